@@ -16,6 +16,15 @@ W untimed warmup iterations, then exactly K timed ones bracketed by a barrier an
 JSON line.  ``value`` is whole-job iterations/s; point-assignments/s and the
 achieved MFMA TFLOP/s are included as extra fields.
 
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed
+steps, the result line.  ``--full`` adds every other measurement as extra fields of the
+same line: clock / power telemetry over the timed steps, the per-phase breakdown, the
+incremental M-step and bounded E-step runs from the same start (cfg3), and cfg4's other
+seedings.  ``--dump-outputs DIR`` writes what the last timed step computed (centres,
+counts, shifts, the step's inertia / changed labels, a fixed seeded sample of the labels)
+as ``DIR/<name>.npy``; the inputs are a function of the arguments alone, so two builds
+can be compared output for output.
+
 Other BASELINE configs (own measurements, not the driver's): ``--config cfg2``
 (N=1e6, D=128, K=256 fp32, one GPU), ``cfg4`` (N=1e7, D=64, K=4096: k-means++
 seeding time + Lloyd it/s), ``cfg5`` (mini-batch, streamed blobs, D=256, K=512).
@@ -29,6 +38,8 @@ import sys
 import time
 
 import torch
+
+DUMP_SAMPLE_ROWS = 1 << 20   # --dump-outputs: labels of this many seeded rows (the full vector where shorter)
 
 METRIC = "Lloyd iterations/sec (and point-assignments/sec) at N=1e8, D=128, K=1024, 1/2/4/8 MI355X"
 
@@ -48,6 +59,13 @@ def main(argv=None):
     ap.add_argument("--config", default="cfg3", choices=sorted(CONFIGS))
     ap.add_argument("--points", "--n", dest="n", type=int, default=None, help="override total points")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (extra fields of the result "
+                         "line): telemetry, phase_ms, cfg3's incremental M-step and bounded E-step runs, "
+                         "cfg4's k-means|| / owner-path / two-stage seedings")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy "
+                         "(float32 / float64; rank 0)")
     ap.add_argument("--batch", type=int, default=1 << 24, help="cfg5 rows per rank per step")
     ap.add_argument("--resident", action="store_true",
                     help="cfg5: batches drawn on the device from an HBM-resident shard of stored rows")
@@ -64,12 +82,12 @@ def main(argv=None):
                          "assign takes them (early prologue) instead of summing its fragments; "
                          "measured slower: assign -0.10 ms, generator +0.14 ms (profiles/r5_68_*)")
     ap.add_argument("--telemetry", action=argparse.BooleanOptionalAction, default=True,
-                    help="sample the GFX clock and socket power (amdsmi, a background thread) over "
-                         "the timed steps")
+                    help="--full: sample the GFX clock and socket power (amdsmi, a background thread) "
+                         "over the timed steps")
     ap.add_argument("--incremental", action="store_true",
                     help="incremental M-step (re-scatter changed rows only; not the headline mode)")
     ap.add_argument("--also-incremental", action=argparse.BooleanOptionalAction, default=True,
-                    help="cfg3: after the timed full-M-step run, time the library default "
+                    help="cfg3 --full: after the timed full-M-step run, time the library default "
                          "(incremental M-step) from the same start and report it as an extra field")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu: gloo rehearsal of the multi-rank path (tests; tiny --n)")
@@ -84,8 +102,8 @@ def main(argv=None):
                          "(cfg2's 0.7 ms steps gain ~1 %%); off for N > 1, where the host already runs "
                          "far ahead of ~3 ms steps")
     ap.add_argument("--also-bounded", action=argparse.BooleanOptionalAction, default=True,
-                    help="cfg3: also time KMeans(algorithm='hamerly')'s bounded E-step from the same start "
-                         "(an extra field)")
+                    help="cfg3 --full: also time KMeans(algorithm='hamerly')'s bounded E-step from the same "
+                         "start (an extra field)")
     ap.add_argument("--kpp-sampling", default="exact", choices=["exact", "two-stage"],
                     help="cfg4 multi-rank k-means++: exact (2 collectives per centre) or two-stage (1)")
     ap.add_argument("--comm", default="rccl", choices=["rccl", "host"],
@@ -135,7 +153,7 @@ def main(argv=None):
     extra = {}
 
     if args.config == "cfg5":
-        value, ms, extra = _bench_minibatch(args, cfg, comm, dtype)
+        value, ms, extra = _bench_minibatch(args, cfg, comm, dtype)   # (writes --dump-outputs itself)
         unit = "points/s"
     else:
         s, e = shard_range(N, comm.rank, world)
@@ -152,7 +170,7 @@ def main(argv=None):
             C0 = init_random(X, D, K, N, s, comm, args.seed)
         sync()
         extra["init_s"] = round(time.perf_counter() - t0, 3)
-        if args.config == "cfg4" and dev.type == "cuda":
+        if args.full and args.config == "cfg4" and dev.type == "cuda":
             # k-means|| (init='k-means||'): ~2 collectives per round instead of per centre;
             # its seeding time and the potential of both seedings, reported beside the bench
             from mikmeans.models.init import init_kmeans_parallel
@@ -170,7 +188,7 @@ def main(argv=None):
             comm.allreduce_(pots)
             extra["init_potential_kpp_vs_kpar"] = [float(pots[0]), float(pots[1])]
             del Ck
-        if args.config == "cfg4" and world == 1 and comm.grouped and dev.type == "cuda":
+        if args.full and args.config == "cfg4" and world == 1 and comm.grouped and dev.type == "cuda":
             # the multi-rank owner path (all-gather of the potentials + owner sampling +
             # all-reduce of the drawn row per step) on the 1-rank RCCL group: its collective
             # overhead against the local path above, same centres
@@ -195,27 +213,33 @@ def main(argv=None):
         eng = LloydEngine(X, K, comm=comm, incremental=args.incremental).set_centers(C0)
         use_graph = args.graph == "on" or (args.graph == "auto" and world == 1)
         extra["graph"] = _capture(eng, use_graph)
-        tel = {} if args.telemetry else None
+        tel = {} if (args.full and args.telemetry) else None
         elapsed = _timed_steps(eng, comm, args.warmup, args.steps, sync, telemetry=tel)
-        tel = tel or {}
-        # the timed steps' mean GFX clock and socket power on rank 0 (null without amdsmi):
-        # value / clock_mhz separates a kernel change from a slower box
-        extra["clock_mhz"] = tel.get("clock_mhz")
-        extra["power_w"] = tel.get("power_w")
-        extra["telemetry"] = tel or None
+        st = eng.last_stats()
+        if args.dump_outputs and comm.rank == 0:
+            # (before anything below steps the engine again)
+            _dump_outputs(args.dump_outputs, args.seed, centers=eng.centers, counts=eng.counts, shift=eng.shift,
+                          stats=[st.inertia, st.n_changed], labels=eng.labels)
+        if args.full:
+            tel = tel or {}
+            # the timed steps' mean GFX clock and socket power on rank 0 (null without amdsmi):
+            # value / clock_mhz separates a kernel change from a slower box
+            extra["clock_mhz"] = tel.get("clock_mhz")
+            extra["power_w"] = tel.get("power_w")
+            extra["telemetry"] = tel or None
         ms = elapsed * 1e3 / args.steps
         value = args.steps / elapsed
         unit = "iter/s"
-        st = eng.last_stats()
         extra.update(
             assignments_per_s=value * N,
             mfma_tflops=2.0 * N * K * D * value / 1e12,
             inertia=st.inertia,
             n_changed=st.n_changed,
-            # one extra, untimed, event-instrumented iteration
-            phase_ms=_phase_breakdown(eng) if (eng.gpu and not args.incremental) else None,
         )
-        if args.config == "cfg3" and args.also_incremental and not args.incremental and eng.gpu:
+        if args.full:
+            # extra, untimed, event-instrumented iterations
+            extra["phase_ms"] = _phase_breakdown(eng) if (eng.gpu and not args.incremental) else None
+        if args.full and args.config == "cfg3" and args.also_incremental and not args.incremental and eng.gpu:
             # extras from the same start (untimed for the headline): a failure there is recorded
             # in the line instead of costing the headline its JSON
             try:
@@ -255,6 +279,28 @@ def main(argv=None):
         print(json.dumps(out), flush=True)
     comm.close()
     return 0
+
+
+def _dump_outputs(out_dir: str, seed: int, *, labels, stats, **arrays) -> None:
+    """``--dump-outputs``: the last timed step's results as ``<name>.npy``.  Small arrays whole
+    (float32; ``stats`` float64); of a label vector longer than DUMP_SAMPLE_ROWS the rows a
+    generator seeded by ``seed`` draws (a function of the seed and the length alone), with
+    their row numbers beside them (float64: exact to 2^53)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to("cpu", torch.float32).contiguous().numpy())
+    np.save(os.path.join(out_dir, "stats.npy"), np.asarray(stats, dtype=np.float64))
+    n = int(labels.shape[0])
+    if n > DUMP_SAMPLE_ROWS:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        rows = torch.randint(n, (DUMP_SAMPLE_ROWS,), generator=g, dtype=torch.int64).sort().values
+        labels = labels[rows.to(labels.device)]
+    else:
+        rows = torch.arange(n, dtype=torch.int64)
+    np.save(os.path.join(out_dir, "labels.npy"), labels.detach().to("cpu", torch.float32).numpy())
+    np.save(os.path.join(out_dir, "label_rows.npy"), rows.to(torch.float64).numpy())
 
 
 def _capture(eng, want: bool):
@@ -458,6 +504,9 @@ def _bench_minibatch(args, cfg, comm, dtype):
     comm.allreduce_max_(t)
     gen_ms, km_ms = float(t[0]), float(t[1])
     pts = args.steps * b * comm.world
+    if args.dump_outputs and comm.rank == 0:
+        _dump_outputs(args.dump_outputs, args.seed, centers=eng.centers, counts=eng.counts, shift=eng.shift,
+                      seen=eng.vcount, stats=[eng.last_batch_inertia()], labels=eng.labels)
     extra.update(mode="resident" if args.resident else "stream", steps_cover_points=pts,
                  gen_ms=round(gen_ms, 4), kmeans_ms=round(km_ms, 4),
                  kmeans_points_per_s=b * comm.world / (km_ms * 1e-3),

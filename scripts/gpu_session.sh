@@ -52,13 +52,13 @@ for s in ${STEPS:-smoke tests bench prof}; do
     ab_g256) step ab_g256 400 python -u scripts/assign_ab.py --d 256 --k 512 --n 125000000 --gather 16777216 \
                --arms "default;assign_geom=1;assign_geom=2;assign_geom=3" ;;
     ab_wide) step ab_wide 300 python -u scripts/assign_ab.py --d 768 --k 1024 --n 4000000 --arms "default" ;;
-    bench) step bench 600 python bench.py --steps ${BENCH_STEPS:-20} --warmup 3 ;;
+    bench) step bench 600 python bench.py --full --steps ${BENCH_STEPS:-20} --warmup 3 ;;
     benchauto) step bench_nopg 600 python bench.py --steps ${BENCH_STEPS:-20} --warmup 3 --pg auto --no-also-incremental ;;
     bench2) step bench_cfg2 300 python bench.py --config cfg2 --steps 50 --warmup 5 ;;
-    bench4) step bench_cfg4 300 python bench.py --config cfg4 --steps 20 --warmup 3 ;;
+    bench4) step bench_cfg4 300 python bench.py --full --config cfg4 --steps 20 --warmup 3 ;;
     bench5) step bench_cfg5 300 python bench.py --config cfg5 --steps 20 --warmup 3 ;;
     bench5r) step bench_cfg5r 300 python bench.py --config cfg5 --resident --steps 20 --warmup 3 ;;
-    bench4ts) step bench_cfg4_2s 300 python bench.py --config cfg4 --steps 20 --warmup 3 --kpp-sampling two-stage ;;
+    bench4ts) step bench_cfg4_2s 300 python bench.py --full --config cfg4 --steps 20 --warmup 3 --kpp-sampling two-stage ;;
     prof5r) cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
           step rocprof5r 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof5r -- python3 bench.py --config cfg5 --resident --steps 5 --warmup 1 ;;
     profb) cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
