@@ -84,7 +84,9 @@ def _spread_rows(n, d, seed, dtype):
 
 
 @pytest.mark.parametrize("d,k", [(64, 96), (128, 256), (256, 64), (512, 40), (64, 2048), (32, 1024), (128, 1024),
-                                 (256, 512), (100, 77)])
+                                 (256, 512), (100, 77),
+                                 # the other wide TOP2 builds (512 is above)
+                                 (384, 40), (768, 40), (1024, 40)])
 def test_gathered_assign_with_seed_offsets_is_the_full_pass(native, d, k):
     """csrc/rows.hip seed_offsets + AssignArgs::oseed: a scattering gathered TOP2 assign over a
     random subset of rows writes bitwise the full pass's distances and labels at those rows --

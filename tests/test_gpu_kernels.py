@@ -831,7 +831,8 @@ def test_overlapped_segments_match_plain_step(native, n, segments):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("n,d,k", [(1000, 2, 3), (20001, 128, 1024), (5000, 64, 4097), (3000, 256, 77),
-                                   (2000, 768, 100), (1500, 1024, 16), (777, 30, 513)])
+                                   (2000, 768, 100), (1500, 1024, 16), (777, 30, 513),
+                                   (1500, 384, 200), (1500, 512, 513)])
 def test_transform_kernel_matches_reference(native, dtype, n, d, k):
     """KMeans.transform's MFMA kernel: every row's distance to every centre against the f64
     distances to the quantised centres; argmin of the row equals the assign's label on rows
