@@ -203,31 +203,60 @@ class _Serving(_Params):
                 Xt = _unit_rows(Xt)
         return Xt, was_numpy
 
-    def _assign_rows(self, X, with_dist: bool, block_rows: int | None = None):
-        """(labels, squared distances or None) of every row of X under the fitted centres.
-        Host rows bound for a GPU model go through in blocks of ~256 MB (or ``block_rows``:
-        a host-shard fit labels its rows in batch-sized blocks, the memory plan's), so a
-        shard larger than HBM (a streamed fit's) is never copied to the device whole."""
-        from . import ops
-
+    def _row_blocks(self, X, run, block_rows: int | None = None):
+        """``run(Xt, pack)`` -- a tuple of per-row tensors (or None) -- over every row of X:
+        ``(outputs, was_numpy)``.  Host rows bound for a GPU model go through in blocks of
+        ~256 MB (or ``block_rows``: a host-shard fit labels its rows in batch-sized blocks,
+        the memory plan's), so a shard larger than HBM (a streamed fit's) is never copied to
+        the device whole."""
         dev = self.cluster_centers_.device
         host = not (torch.is_tensor(X) and X.device == dev)
         n = X.shape[0]
         if dev.type != "cuda" or not host or n == 0:
             Xt, was_numpy = self._inputs(X)
-            lab, mind = ops.assign(Xt, self.cluster_centers_, with_dist=with_dist, pack=self._serving_pack(Xt))
-            return lab, mind, was_numpy
+            return tuple(run(Xt, self._serving_pack(Xt))), was_numpy
         was_numpy = not torch.is_tensor(X)
         block = int(block_rows) if block_rows else max(1, (1 << 28) // max(1, X.shape[1] * 4))
-        labels = torch.empty(n, dtype=torch.int32, device=dev)
-        mind = torch.empty(n, dtype=torch.float32, device=dev) if with_dist else None
+        outs = None
         for i in range(0, n, block):
             Xt, _ = self._inputs(X[i : i + block])
-            lab, md = ops.assign(Xt, self.cluster_centers_, with_dist=with_dist, pack=self._serving_pack(Xt))
-            labels[i : i + block] = lab
-            if with_dist:
-                mind[i : i + block] = md
-        return labels, mind, was_numpy
+            part = run(Xt, self._serving_pack(Xt))
+            if outs is None:
+                outs = [None if p is None else torch.empty((n, *p.shape[1:]), dtype=p.dtype, device=dev)
+                        for p in part]
+            for o, p in zip(outs, part):
+                if o is not None:
+                    o[i : i + block] = p
+        return tuple(outs), was_numpy
+
+    def _assign_rows(self, X, with_dist: bool, block_rows: int | None = None):
+        """(labels, squared distances or None) of every row of X under the fitted centres
+        (host rows in blocks, :meth:`_row_blocks`)."""
+        from . import ops
+
+        (lab, mind), was_numpy = self._row_blocks(
+            X, lambda Xt, pk: ops.assign(Xt, self.cluster_centers_, with_dist=with_dist, pack=pk), block_rows)
+        return lab, mind, was_numpy
+
+    def predict_topk(self, X, m: int, *, squared: bool = False, block_rows: int | None = None):
+        """The ``m`` nearest centres of every row with their distances: ``(labels [n, m]
+        int32, distances [n, m] float32)``, nearest first and equal distances by centre index.
+        Distances are Euclidean as in :meth:`transform` (``squared``: the kernel's squared
+        values; for the cosine metric between unit rows and unit centres).  On the GPU the
+        fused top-m kernel on the serving pack (csrc/topk.hip) -- the ``[n, K]`` distance
+        matrix is never written.  numpy in, numpy out; host rows bound for a GPU model go
+        through in blocks (``block_rows``) as in :meth:`predict`."""
+        from . import ops
+
+        self._check_fitted()
+        m = int(m)
+        K = int(self.cluster_centers_.shape[0])
+        if not 1 <= m <= K:
+            raise ValueError(f"predict_topk needs 1 <= m <= n_clusters ({K}), got m = {m}")
+        (idx, d2), was_numpy = self._row_blocks(
+            X, lambda Xt, pk: ops.topk(Xt, self.cluster_centers_, m, pack=pk), block_rows)
+        d = d2 if squared else d2.sqrt()
+        return (idx.cpu().numpy(), d.cpu().numpy()) if was_numpy else (idx, d)
 
     def transform(self, X):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine
@@ -1028,6 +1057,20 @@ def predict(X, centers, dtype="float32"):
     Xt, _ = _to_tensor(X, dev, resolve_dtype(dtype))
     labels, _ = ops.assign(Xt, c.to(dev), with_dist=False)
     return labels.cpu().numpy() if was_numpy else labels
+
+
+def predict_topk(X, centers, m: int, dtype="float32"):
+    """The ``m`` nearest of the given ``centers`` for every row of ``X``: ``(labels [n, m],
+    Euclidean distances [n, m])``, nearest first (``KMeans.predict_topk`` without a model)."""
+    from . import ops
+
+    was_numpy = not torch.is_tensor(X)
+    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
+    dev = c.device if torch.is_tensor(centers) else _default_device(None)
+    Xt, _ = _to_tensor(X, dev, resolve_dtype(dtype))
+    idx, d2 = ops.topk(Xt, c.to(dev), m)
+    d = d2.sqrt()
+    return (idx.cpu().numpy(), d.cpu().numpy()) if was_numpy else (idx, d)
 
 
 def fit_predict(X, k: int, **kw):

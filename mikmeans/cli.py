@@ -106,13 +106,28 @@ def cmd_predict(a) -> int:
     comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     km = KMeans.load(a.model, device=comm.device)
     X, n, start = load_points(a.input, comm.rank, comm.world)
-    lab = km.predict(X.to(comm.device))
+    def _save(path, arr):
+        np.save(Path(path).with_suffix(f".rank{comm.rank}.npy") if comm.world > 1 else path, arr,
+                allow_pickle=False)
+
+    if a.distances_output and not a.top:
+        raise SystemExit("predict: --distances-output needs --top M")
+    if a.top:
+        # the M nearest centres of every row, nearest first: [n, M] labels (and distances)
+        if not 1 <= a.top <= km.cluster_centers_.shape[0]:
+            raise SystemExit(f"predict: --top must be in [1, {km.cluster_centers_.shape[0]}], got {a.top}")
+        lab, dist = km.predict_topk(X.to(comm.device), a.top)
+        dist = dist.cpu().numpy().astype(np.float32)
+        if a.distances_output:
+            _save(a.distances_output, dist)
+    else:
+        lab = km.predict(X.to(comm.device))
     lab = lab.cpu().numpy().astype(np.int32)
     if a.output:
-        np.save(Path(a.output).with_suffix(f".rank{comm.rank}.npy") if comm.world > 1 else a.output, lab,
-                allow_pickle=False)
+        _save(a.output, lab)
     if comm.rank == 0:
-        print(json.dumps({"n_samples": n, "counts": np.bincount(lab, minlength=km.n_clusters).tolist()}))
+        nearest = lab[:, 0] if a.top else lab
+        print(json.dumps({"n_samples": n, "counts": np.bincount(nearest, minlength=km.n_clusters).tolist()}))
     comm.close()
     return 0
 
@@ -370,6 +385,9 @@ def build_parser():
     p.add_argument("--model", required=True)
     p.add_argument("--input", required=True)
     p.add_argument("--output")
+    p.add_argument("--top", type=int, default=0, metavar="M",
+                   help="write the M nearest centres of every row, nearest first ([n, M] labels)")
+    p.add_argument("--distances-output", metavar="PATH", help="with --top: the [n, M] distances (.npy)")
     p.add_argument("--device")
     b = sub.add_parser("blobs", help="write a synthetic dataset")
     b.add_argument("--n", type=int, required=True)

@@ -173,6 +173,33 @@ void transform(const Tensor& X, const Tensor& pack, const Tensor& cn, int64_t K,
   hip_check(mk::launch_transform(dt, (int)dpad, a, stream()), "transform");
 }
 
+void topk(const Tensor& X, const Tensor& pack, const Tensor& cn, int64_t K, int64_t Kpad, int64_t dpad,
+          const Tensor& xn, const Tensor& dist, const Tensor& idx) {
+  const int dt = dtype_of(X);
+  const int64_t ldx = check_points(X, dt);
+  const int64_t N = X.size(0);
+  TORCH_CHECK(X.size(1) <= dpad, "mikmeans: D exceeds dpad");
+  TORCH_CHECK(K >= 1 && mk::assign_kpad(dt, (int)dpad, (int)K) == Kpad, "mikmeans: bad Kpad ", Kpad);
+  check_cuda(pack, "pack");
+  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == X.scalar_type() && pack.numel() >= Kpad * dpad,
+              "mikmeans: pack must be the points' dtype, [Kpad * dpad]");
+  check_f32(cn, "cn", Kpad);
+  check_f32(xn, "xn", N);
+  TORCH_CHECK(dist.dim() == 2 && dist.size(0) == N, "mikmeans: dist must be [N, m]");
+  const int64_t m = dist.size(1);
+  TORCH_CHECK(m >= 1 && m <= K && m <= mk::TOPK_MAX, "mikmeans: topk needs 1 <= m <= min(K, ", mk::TOPK_MAX,
+              "), got m = ", m, " for K = ", K);
+  check_f32(dist, "dist", N * m);
+  check_i32(idx, "idx", N * m);
+  TORCH_CHECK(idx.dim() == 2 && idx.size(0) == N && idx.size(1) == m, "mikmeans: idx must be [N, m]");
+  mk::TopkArgs a;
+  a.X = X.data_ptr(); a.N = N; a.D = (int)X.size(1); a.ldx = ldx;
+  a.pack = pack.data_ptr(); a.cn = cn.data_ptr<float>(); a.K = (int)K; a.Kpad = (int)Kpad;
+  a.xn = xn.data_ptr<float>();
+  a.dist = dist.data_ptr<float>(); a.idx = idx.data_ptr<int32_t>(); a.m = (int)m;
+  hip_check(mk::launch_topk(dt, (int)dpad, a, stream()), "topk");
+}
+
 void check_i64(const Tensor& t, const char* name, int64_t numel_min) {
   check_cuda(t, name);
   TORCH_CHECK(t.scalar_type() == at::kLong && t.is_contiguous(), "mikmeans: ", name,
@@ -795,6 +822,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transform", &transform, "distances of every row to every centre on the MFMA tiles", py::arg("X"),
         py::arg("pack"), py::arg("cn"), py::arg("K"), py::arg("Kpad"), py::arg("dpad"), py::arg("xn"), py::arg("out"),
         py::arg("squared") = false);
+  m.def("topk", &topk, "the m nearest centres of every row (squared distances, ascending) on the MFMA tiles",
+        py::arg("X"), py::arg("pack"), py::arg("cn"), py::arg("K"), py::arg("Kpad"), py::arg("dpad"), py::arg("xn"),
+        py::arg("dist"), py::arg("idx"));
   m.def("reduce_cols", &reduce_cols, "lo sums of the wide-range columns (residual pass)");
   m.def("reduce", &reduce, "slab reduction into the packed f64 all-reduce message");
   m.def("label_delta", &label_delta, "changed-row list for the incremental M-step");

@@ -103,6 +103,20 @@ struct TransformArgs {
 };
 hipError_t launch_transform(int dtype, int dpad, const TransformArgs& a, hipStream_t s);
 
+// ---- top-m: every row's m nearest centres (csrc/topk.hip) -------------------------------
+// dist[i, j], idx[i, j] = the j-th smallest (squared distance, centre) pair of row i, the
+// squared distances bitwise launch_transform's, ties to the lower centre index; 1 <= m <= min(K, TOPK_MAX).
+constexpr int TOPK_MAX = 32;
+struct TopkArgs {
+  const void* X; int64_t N; int D; int64_t ldx;
+  const void* pack; const float* cn; int K; int Kpad;   // the assign kernel's packed centres
+  const float* xn;      // |x|^2 per row
+  float* dist;          // [N, m] squared distances, ascending
+  int32_t* idx;         // [N, m] their centres
+  int m;
+};
+hipError_t launch_topk(int dtype, int dpad, const TopkArgs& a, hipStream_t s);
+
 // ---- Hamerly bounds (csrc/rows.hip) ----------------------------------------------------
 // Moves every point's bounds by the last M-step's centre shifts (ub += |dc_label|,
 // lb -= the largest |dc_k| over k != label) and flags the points whose bounds no longer prove

@@ -194,6 +194,49 @@ def transform(X: torch.Tensor, centers: torch.Tensor, *, squared: bool = False,
     return out
 
 
+TOPK_NATIVE_MAX = 32      # the top-m kernel's longest list (csrc/kernels.h TOPK_MAX)
+
+
+def topk(X: torch.Tensor, centers: torch.Tensor, m: int, *, pack: "CentroidPack | None" = None):
+    """The ``m`` nearest centres of every row: ``(idx int32 [n, m], d2 float32 [n, m])``, the
+    squared distances ascending and equal ones by centre index -- the first ``m`` columns of a
+    stable sort of ``transform(X, centers, squared=True)``, bit for bit.  On the GPU the fused
+    MFMA kernel (csrc/topk.hip) keeps the ``m <= 32`` best in registers, so the ``[n, K]``
+    matrix is never written; a longer list sorts the transform kernel's distances in row
+    blocks of ~256 MB.  ``pack`` as in :func:`transform`.  Elsewhere the PyTorch reference."""
+    m = int(m)
+    K = centers.shape[0]
+    if not 1 <= m <= K:
+        raise ValueError(f"topk needs 1 <= m <= n_clusters ({K}), got m = {m}")
+    if not X.is_cuda or dpad_for(pad_columns(X[:1]).shape[1], X.dtype) == 0:
+        return cpu.topk(X, centers.to(X.device), m)  # CPU, or D > 1024 on the GPU
+    C = require()
+    Xp = pad_columns(X)
+    D = Xp.shape[1]
+    if pack is not None and (pack.D, pack.dtype, pack.pack.device) == (D, Xp.dtype, Xp.device):
+        pk = pack
+    else:
+        pk = pack_centers(centers, D, Xp.dtype, X.device)
+    n = Xp.shape[0]
+    idx = torch.empty((n, m), dtype=torch.int32, device=X.device)
+    d2 = torch.empty((n, m), dtype=torch.float32, device=X.device)
+    if n == 0:
+        return idx, d2
+    if m <= TOPK_NATIVE_MAX:
+        xn = torch.empty(n, dtype=torch.float32, device=X.device)
+        C.row_sqnorm(Xp, xn)
+        C.topk(Xp, pk.pack, pk.cn, pk.K, pk.Kpad, pk.dpad, xn, d2, idx)
+        return idx, d2
+    # distances, their sorted copy and int64 indices: 16 B per (row, centre)
+    rows = max(1, (1 << 28) // (16 * K))
+    for s in range(0, n, rows):
+        d = transform(Xp[s : s + rows], centers, squared=True, pack=pk)
+        v, i = torch.sort(d, dim=1, stable=True)
+        d2[s : s + rows] = v[:, :m]
+        idx[s : s + rows] = i[:, :m].to(torch.int32)
+    return idx, d2
+
+
 def max_abs(X: torch.Tensor) -> float:
     """max |x| without materialising |X| (one host read)."""
     if X.numel() == 0:

@@ -48,6 +48,25 @@ def assign(X: torch.Tensor, centers: torch.Tensor, *, with_dist: bool = True, xn
     return labels, mind
 
 
+def topk(X: torch.Tensor, centers: torch.Tensor, m: int):
+    """The ``m`` nearest centres of every row: ``(idx int32 [n, m], d2 float32 [n, m])``, the
+    float32 squared distances to the quantised centres ascending, equal ones by centre index
+    (a stable sort)."""
+    c = quantize_centers(centers, X.dtype)
+    n = X.shape[0]
+    idx = torch.empty((n, m), dtype=torch.int32, device=X.device)
+    d2 = torch.empty((n, m), dtype=torch.float32, device=X.device)
+    cn = (c * c).sum(1)
+    for s in range(0, n, _CHUNK):
+        xb = X[s : s + _CHUNK].to(torch.float32)
+        # |x|^2 + (|c|^2 - 2 x.c), clamped: the form the kernels (and assign above) evaluate
+        d = ((xb * xb).sum(1)[:, None] + (cn[None, :] - 2.0 * (xb @ c.T))).clamp_min(0.0)
+        v, i = torch.sort(d, dim=1, stable=True)
+        d2[s : s + _CHUNK] = v[:, :m]
+        idx[s : s + _CHUNK] = i[:, :m].to(torch.int32)
+    return idx, d2
+
+
 def cluster_sums(X: torch.Tensor, labels: torch.Tensor, K: int, weights=None):
     lab = labels.to(torch.int64)
     Xd = X.to(torch.float64)

@@ -37,7 +37,8 @@ Endpoints (JSON in and out) -- the reference's controls (``index.html:76-131``,
 * ``GET /api/model`` the served model's shape and centroids, ``GET /api/model/centroids.json``
   the flat-float centroid array byte-identical to a saved ``centroids.json``
   (:func:`~mikmeans.utils.jsjson.centroids_to_json`); ``POST /api/predict``
-  {points[, distances]} -> labels (and squared distances), ``POST /api/predict.npy`` (a
+  {points[, distances][, top]} -> labels (and squared distances; with ``top`` = m the m
+  nearest centres of every row, nearest first, as lists of m), ``POST /api/predict.npy`` (a
   ``.npy`` body in, ``.npy`` labels out), ``POST /api/transform``.
 
 Request bodies over ``max_body_bytes`` get 413 -- declared or counted as they stream in (chunked) --
@@ -866,6 +867,18 @@ def create_app(room: Room | None = None, model=None, *, device=None, max_body_by
     def predict(body: dict = Body(...)):
         m = _model()
         X = _points(body)
+        if "top" in body:
+            # the `top` nearest centres of every row, nearest first: labels (and squared
+            # distances) become lists of `top` values per row
+            top, K = body["top"], int(m.cluster_centers_.shape[0])
+            if isinstance(top, bool) or not isinstance(top, int) or not 1 <= top <= K:
+                raise HTTPException(400, f"top: an integer in [1, {K}]")
+            with model_lock:
+                idx, d2 = m.predict_topk(X, top, squared=True)
+            out = {"labels": idx.cpu().tolist()}
+            if bool(body.get("distances", False)):
+                out["distances"] = d2.cpu().tolist()
+            return out
         with model_lock:
             labels, mind, _ = m._assign_rows(X, bool(body.get("distances", False)))
         out = {"labels": labels.cpu().tolist()}
