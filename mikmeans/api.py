@@ -16,6 +16,7 @@ iteration counter + metric snapshots (R23/R31, app.mjs:288, :498-508) ->
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import time
 
@@ -111,6 +112,89 @@ def _shard_info(n_local: int, comm: Comm, device):
     sizes = comm.all_gather(torch.tensor([n_local], dtype=torch.int64, device=device)).reshape(-1).cpu()
     start = int(sizes[: comm.rank].sum())
     return int(sizes.sum()), start
+
+
+def _jsonable(v):
+    """Plain JSON values: lists for arrays, None for NaN, "Infinity" for an infinite float."""
+    if isinstance(v, dict):
+        return {k: _jsonable(x) for k, x in v.items()}
+    if torch.is_tensor(v) or isinstance(v, np.ndarray):
+        v = v.tolist()
+    if isinstance(v, (list, tuple)):
+        return [_jsonable(x) for x in v]
+    if isinstance(v, float) and not math.isfinite(v):
+        return None if math.isnan(v) else ("Infinity" if v > 0 else "-Infinity")
+    return v
+
+
+@dataclasses.dataclass(eq=False)
+class ClusterReport:
+    """Per-cluster quality of a data set under fitted centres (``cluster_report``).
+
+    Per cluster, ``[K]`` (tensors on the model's device, NumPy arrays for NumPy input):
+    ``counts`` (rows with a finite distance), ``cluster_inertia`` (sum of squared distances),
+    ``mean_distance``, ``rms_distance``, ``radius`` (the largest distance),
+    ``cluster_silhouette`` (mean simplified silhouette 1 - a / b: a the distance to the own,
+    b to the second-nearest centre) and ``n_nonfinite`` (rows left out because their distance
+    is NaN or infinite).  Empty clusters have NaN means and radius 0.  Totals: ``n_samples``,
+    ``inertia``, ``silhouette`` (NaN for one cluster), ``davies_bouldin`` (on the mean
+    distances and the centre separations; NaN with fewer than two non-empty clusters) and
+    ``balance`` ({max, min, gap, ratio} of the counts).  ``table`` is the int64
+    ``[K, QUALITY_WORDS]`` reduction everything was decoded from (csrc/quality.hip)."""
+
+    counts: object
+    cluster_inertia: object
+    mean_distance: object
+    rms_distance: object
+    radius: object
+    cluster_silhouette: object
+    n_nonfinite: object
+    n_samples: int
+    inertia: float
+    silhouette: float
+    davies_bouldin: float
+    balance: dict
+    table: object
+
+    PER_CLUSTER = ("counts", "cluster_inertia", "mean_distance", "rms_distance", "radius", "cluster_silhouette",
+                   "n_nonfinite")
+
+    @classmethod
+    def from_table(cls, table: torch.Tensor, centers: torch.Tensor, dtype):
+        from . import ops
+
+        rep = ops.quality_decode(table, centers, dtype)
+        for k in cls.PER_CLUSTER:
+            rep[k] = rep[k].to(table.device)
+        return cls(table=table, **rep)
+
+    def numpy(self) -> "ClusterReport":
+        """The same report with NumPy arrays."""
+        return dataclasses.replace(self, table=self.table.cpu().numpy(),
+                                   **{k: getattr(self, k).cpu().numpy() for k in self.PER_CLUSTER})
+
+    def to_dict(self) -> dict:
+        """Plain lists, ints and floats (NaN as None, an infinite ratio as "Infinity")."""
+        out = {k: getattr(self, k) for k in ("n_samples", "inertia", "silhouette", "davies_bouldin", "balance")}
+        out["n_clusters"] = len(self.counts)
+        out["n_nonfinite"] = int(self.n_nonfinite.sum())
+        out["clusters"] = {k: getattr(self, k) for k in self.PER_CLUSTER}
+        return _jsonable(out)
+
+
+def _report_table(centers, comm, dtype, fold) -> ClusterReport:
+    """``fold(table)`` accumulates this rank's rows; the table is then summed (its maximum
+    word maximised) over the ranks of ``comm`` and decoded, the same on every rank."""
+    from . import ops
+
+    table = torch.zeros((centers.shape[0], ops.QUALITY_WORDS), dtype=torch.int64, device=centers.device)
+    fold(table)
+    if comm is not None and comm.grouped:
+        mx = table[:, 17].clone()
+        comm.allreduce_(table)
+        comm.allreduce_max_(mx)
+        table[:, 17] = mx
+    return ClusterReport.from_table(table, centers, dtype)
 
 
 class _Params:
@@ -257,6 +341,46 @@ class _Serving(_Params):
             X, lambda Xt, pk: ops.topk(Xt, self.cluster_centers_, m, pack=pk), block_rows)
         d = d2 if squared else d2.sqrt()
         return (idx.cpu().numpy(), d.cpu().numpy()) if was_numpy else (idx, d)
+
+    def _fold_blocks(self, X, run, block_rows: int | None = None) -> None:
+        """``run(Xt, pack)`` over every row of X for its side effect (an accumulation), host
+        rows bound for a GPU model in blocks as :meth:`_row_blocks` takes them."""
+        dev = self.cluster_centers_.device
+        host = not (torch.is_tensor(X) and X.device == dev)
+        n = X.shape[0]
+        block = n if dev.type != "cuda" or not host or n == 0 else (
+            int(block_rows) if block_rows else max(1, (1 << 28) // max(1, X.shape[1] * 4)))
+        for i in range(0, max(n, 1), max(block, 1)):
+            Xt, _ = self._inputs(X[i : i + block] if block < n else X)
+            run(Xt, self._serving_pack(Xt))
+
+    def cluster_report(self, X, *, block_rows: int | None = None) -> ClusterReport:
+        """Per-cluster quality of ``X`` under the fitted centres, a :class:`ClusterReport`:
+        every cluster's size, inertia, mean and rms distance, radius and simplified
+        silhouette, and the totals (inertia, silhouette, Davies-Bouldin index, balance).
+
+        One fused pass: the top-2 kernel (:meth:`predict_topk`'s, on the serving pack) gives
+        each row's nearest and second-nearest centre, and csrc/quality.hip folds them into an
+        integer table per cluster -- no ``[n, K]`` matrix, no floating-point add on the
+        reduction path, so the report is bitwise the same from run to run, for any
+        ``block_rows`` (rows per top-2 pass; host rows bound for a GPU model are also copied
+        in blocks of that size) and, in a multi-rank job where ``X`` is the rank's shard, on
+        any world size (the table is all-reduced; every rank returns the same report).
+
+        A row's cluster is :meth:`predict_topk`'s first column: the exact nearest centre, the
+        lower index on ties.  For bfloat16 that can differ from :meth:`predict` on near-ties,
+        which ranks by packed keys.  Cosine models report on unit rows.  numpy in, numpy out."""
+        from . import ops
+
+        self._check_fitted()
+        c = self.cluster_centers_
+
+        def fold(table):
+            self._fold_blocks(X, lambda Xt, pk: ops.quality_rows(table, Xt, c, pack=pk, block_rows=block_rows),
+                              block_rows)
+
+        rep = _report_table(c, getattr(self, "comm", None) or get_comm(), self.dtype, fold)
+        return rep if torch.is_tensor(X) else rep.numpy()
 
     def transform(self, X):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine
@@ -1071,6 +1195,21 @@ def predict_topk(X, centers, m: int, dtype="float32"):
     idx, d2 = ops.topk(Xt, c.to(dev), m)
     d = d2.sqrt()
     return (idx.cpu().numpy(), d.cpu().numpy()) if was_numpy else (idx, d)
+
+
+def cluster_report(X, centers, dtype="float32") -> ClusterReport:
+    """Per-cluster quality of ``X`` under the given ``centers``
+    (``KMeans.cluster_report`` without a model; with a process group ``X`` is the rank's shard)."""
+    from . import ops
+
+    was_numpy = not torch.is_tensor(X)
+    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
+    dev = c.device if torch.is_tensor(centers) else _default_device(None)
+    dt = resolve_dtype(dtype)
+    Xt, _ = _to_tensor(X, dev, dt)
+    c = c.to(dev)
+    rep = _report_table(c, get_comm(), dt, lambda table: ops.quality_rows(table, Xt, c))
+    return rep.numpy() if was_numpy else rep
 
 
 def fit_predict(X, k: int, **kw):

@@ -5,6 +5,8 @@ Commands (the reference's top-bar controls, app.mjs:240-288, as a CLI):
 * ``fit``      -- k-means on a file (.npy/.safetensors/.csv) or synthetic blobs; writes a
                   checkpoint (safetensors + JSON), the flat-float ``centroids.json`` and labels
 * ``predict``  -- labels of a dataset under a saved model
+* ``report``   -- per-cluster quality of a dataset under a saved model (sizes, inertia, radius,
+                  simplified silhouette, Davies-Bouldin), as JSON
 * ``blobs``    -- write a synthetic Gaussian-blob dataset
 * ``room``     -- the trait-card game headless: seed/populate/auto-assign/dashboard/export/import
 * ``session``  -- one participant of a live, replicated room session: found it (hosting the
@@ -128,6 +130,24 @@ def cmd_predict(a) -> int:
     if comm.rank == 0:
         nearest = lab[:, 0] if a.top else lab
         print(json.dumps({"n_samples": n, "counts": np.bincount(nearest, minlength=km.n_clusters).tolist()}))
+    comm.close()
+    return 0
+
+
+def cmd_report(a) -> int:
+    """Per-cluster quality of a dataset under a saved model (``KMeans.cluster_report``): every
+    rank folds its shard, the integer table is all-reduced, rank 0 writes the report."""
+    from . import KMeans
+    from .utils.io import load_points
+
+    comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    km = KMeans.load(a.model, device=comm.device)
+    X, n, start = load_points(a.input, comm.rank, comm.world)
+    rep = km.cluster_report(X.to(comm.device)).to_dict()
+    if comm.rank == 0:
+        if a.output:
+            Path(a.output).write_text(json.dumps(rep, indent=1))
+        print(json.dumps({k: rep[k] for k in ("n_samples", "inertia", "silhouette", "davies_bouldin", "balance")}))
     comm.close()
     return 0
 
@@ -389,6 +409,11 @@ def build_parser():
                    help="write the M nearest centres of every row, nearest first ([n, M] labels)")
     p.add_argument("--distances-output", metavar="PATH", help="with --top: the [n, M] distances (.npy)")
     p.add_argument("--device")
+    rp = sub.add_parser("report", help="per-cluster quality of a dataset under a saved model")
+    rp.add_argument("--model", required=True)
+    rp.add_argument("--input", required=True)
+    rp.add_argument("--output", help="write the whole report here as JSON")
+    rp.add_argument("--device")
     b = sub.add_parser("blobs", help="write a synthetic dataset")
     b.add_argument("--n", type=int, required=True)
     b.add_argument("--d", type=int, required=True)
@@ -486,7 +511,7 @@ def main(argv=None) -> int:
         a, rest = la.parse_known_args(argv[1:])
         return cmd_launch(a, rest)
     a = build_parser().parse_args(argv)
-    return {"fit": cmd_fit, "predict": cmd_predict, "blobs": cmd_blobs, "room": cmd_room, "session": cmd_session,
+    return {"fit": cmd_fit, "predict": cmd_predict, "report": cmd_report, "blobs": cmd_blobs, "room": cmd_room, "session": cmd_session,
             "export": cmd_export, "import": cmd_import, "info": cmd_info, "plan": cmd_plan,
             "serve": cmd_serve}[a.cmd](a)
 

@@ -207,6 +207,30 @@ void check_i64(const Tensor& t, const char* name, int64_t numel_min) {
   TORCH_CHECK(t.numel() >= numel_min, "mikmeans: ", name, " too small");
 }
 
+void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {
+  TORCH_CHECK(idx.dim() == 2 && d2.dim() == 2 && idx.size(0) == d2.size(0) && idx.size(1) == d2.size(1),
+              "mikmeans: idx and d2 must both be [N, m]");
+  const int64_t N = idx.size(0), m = idx.size(1);
+  TORCH_CHECK(m == 1 || m == 2, "mikmeans: quality_accumulate needs m = 1 or 2, got ", m);
+  check_i32(idx, "idx", N * m);
+  check_f32(d2, "d2", N * m);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(d2.data_ptr()) % 8 == 0, "mikmeans: d2 must be 8-B aligned");
+  TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUALITY_WORDS, "mikmeans: table must be [K, ",
+              mk::QUALITY_WORDS, "]");
+  check_i64(table, "table", mk::QUALITY_WORDS);
+  TORCH_CHECK(table.size(0) <= INT32_MAX, "mikmeans: too many clusters");
+  TORCH_CHECK(idx.get_device() == table.get_device() && d2.get_device() == table.get_device(),
+              "mikmeans: idx, d2 and table must share a device");
+  mk::QualityArgs a;
+  a.idx = idx.data_ptr<int32_t>(); a.dist = d2.data_ptr<float>(); a.N = N; a.m = (int)m;
+  a.K = (int)table.size(0);
+  a.table = reinterpret_cast<unsigned long long*>(table.data_ptr<int64_t>());
+  TORCH_CHECK(path >= -1 && path <= 1 && (path < 1 || a.K <= mk::QUALITY_LDS_MAX_K),
+              "mikmeans: quality_accumulate path must be -1 (rule), 0 (global) or 1 (LDS, K <= ",
+              mk::QUALITY_LDS_MAX_K, ")");
+  hip_check(mk::launch_quality(a, stream(), (int)path), "quality_accumulate");
+}
+
 void update(const Tensor& X, const Tensor& labels, int64_t K, const Tensor& slab,
             const Tensor& cnt_slab, int64_t n_chunks, const c10::optional<Tensor>& weights,
             const Tensor& col_exp, int64_t cnt_exp, bool clamp,
@@ -825,6 +849,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk", &topk, "the m nearest centres of every row (squared distances, ascending) on the MFMA tiles",
         py::arg("X"), py::arg("pack"), py::arg("cn"), py::arg("K"), py::arg("Kpad"), py::arg("dpad"), py::arg("xn"),
         py::arg("dist"), py::arg("idx"));
+  m.def("quality_accumulate", &quality_accumulate,
+        "add the top-2 output's per-cluster quality words into table [K, QUALITY_WORDS] (integer atomics)",
+        py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("path") = -1);
+  m.def("quality_uses_lds", [](int64_t N, int64_t K) { return mk::quality_uses_lds(N, (int)K); },
+        "whether a batch of N rows over K labels takes the LDS-private kernel");
+  m.attr("QUALITY_WORDS") = mk::QUALITY_WORDS;
+  m.attr("QUALITY_PASS_ROWS") = (int64_t)mk::QUALITY_MAX_BLOCKS * mk::QUALITY_THREADS;
+  m.attr("QUALITY_LDS_PASS_ROWS") = (int64_t)mk::QUALITY_LDS_BLOCKS * mk::QUALITY_LDS_THREADS;
+  m.attr("QUALITY_LDS_MAX_K") = mk::QUALITY_LDS_MAX_K;
+  m.attr("QUALITY_LDS_MIN_ROWS") = mk::QUALITY_LDS_MIN_ROWS;
   m.def("reduce_cols", &reduce_cols, "lo sums of the wide-range columns (residual pass)");
   m.def("reduce", &reduce, "slab reduction into the packed f64 all-reduce message");
   m.def("label_delta", &label_delta, "changed-row list for the incremental M-step");

@@ -117,6 +117,30 @@ struct TopkArgs {
 };
 hipError_t launch_topk(int dtype, int dpad, const TopkArgs& a, hipStream_t s);
 
+// ---- per-cluster quality table (csrc/quality.hip) ----------------------------------------
+// Folds launch_topk's output (m = 1 or 2) into table[K][QUALITY_WORDS] (u64, only ever added
+// into) with integer atomics: per label the digits of sum a^2 and the row count, the digits of
+// sum a, the non-finite rows, the fixed-point simplified-silhouette sum and the largest a^2.
+constexpr int QUALITY_WORDS = 24;
+constexpr int QUALITY_THREADS = 256;
+constexpr int QUALITY_MAX_BLOCKS = 2048;   // rows past QUALITY_MAX_BLOCKS * QUALITY_THREADS: the grid-stride loop
+// The LDS-private form: words 0..17 of every label in one workgroup's LDS (<= 160 KiB), one
+// 1024-thread workgroup per CU, taken for K <= QUALITY_LDS_MAX_K and N >= QUALITY_LDS_MIN_ROWS.
+constexpr int QUALITY_LDS_WORDS = 18;
+constexpr int QUALITY_LDS_THREADS = 1024;
+constexpr int QUALITY_LDS_BLOCKS = 256;
+constexpr int QUALITY_LDS_MAX_K = 160 * 1024 / (QUALITY_LDS_WORDS * 8);   // 1137
+constexpr int QUALITY_LDS_MIN_ROWS = 8192;
+struct QualityArgs {
+  const int32_t* idx;          // [N, m] centres, nearest first
+  const float* dist;           // [N, m] their squared distances
+  int64_t N; int m; int K;
+  unsigned long long* table;   // [K, QUALITY_WORDS]
+};
+// path: -1 the rule above (quality_uses_lds), 0 the global-atomic kernel, 1 the LDS-private one.
+bool quality_uses_lds(int64_t N, int K);
+hipError_t launch_quality(const QualityArgs& a, hipStream_t s, int path = -1);
+
 // ---- Hamerly bounds (csrc/rows.hip) ----------------------------------------------------
 // Moves every point's bounds by the last M-step's centre shifts (ub += |dc_label|,
 // lb -= the largest |dc_k| over k != label) and flags the points whose bounds no longer prove

@@ -28,6 +28,9 @@ __all__ = [
     "assign",
     "cluster_sums",
     "CentroidPack",
+    "quality_accumulate",
+    "quality_decode",
+    "cluster_quality",
 ]
 
 
@@ -235,6 +238,128 @@ def topk(X: torch.Tensor, centers: torch.Tensor, m: int, *, pack: "CentroidPack 
         d2[s : s + rows] = v[:, :m]
         idx[s : s + rows] = i[:, :m].to(torch.int32)
     return idx, d2
+
+
+QUALITY_WORDS = cpu.QUALITY_WORDS   # csrc/kernels.h (the extension exports the same number)
+QUALITY_BLOCK_ROWS = 1 << 22        # rows per top-2 pass of cluster_quality: 64 MB of (idx, d2) scratch
+
+
+def quality_accumulate(table: torch.Tensor, idx: torch.Tensor, d2: torch.Tensor, *, path: int = -1) -> torch.Tensor:
+    """Add the per-cluster quality words of a top-1 / top-2 result (``idx`` int32, ``d2``
+    float32, ``[n, 1 or 2]`` as :func:`topk` returns them) into ``table`` (int64
+    ``[K, QUALITY_WORDS]``, zero before the first call): per label the exact digits of the
+    sum of squared distances and the row count, the digits of the sum of distances, the
+    non-finite rows, the fixed-point simplified-silhouette sum and the largest squared
+    distance (csrc/quality.hip has the layout).  Integer atomics only, so the table does not
+    depend on the order or the blocking of the rows.  GPU tensors run the native kernel
+    (``path``: 0 forces its global-atomic form, 1 the LDS-private one, -1 the launcher's rule:
+    tests and A/B runs), others the integer mirror :func:`mikmeans.ops.cpu.quality_table`."""
+    if table.dim() != 2 or table.shape[1] != QUALITY_WORDS or table.dtype != torch.int64:
+        raise ValueError(f"quality_accumulate needs an int64 [K, {QUALITY_WORDS}] table")
+    if idx.is_cuda:
+        C = require()
+        assert C.QUALITY_WORDS == QUALITY_WORDS
+        C.quality_accumulate(idx.contiguous(), d2.contiguous(), table, path)
+        return table
+    part = cpu.quality_table(idx, d2, table.shape[0])
+    mx = torch.maximum(table[:, 17], part[:, 17])
+    table += part
+    table[:, 17] = mx
+    return table
+
+
+def _slot_value(W: torch.Tensor) -> torch.Tensor:
+    """f64 value of summed digit words ``W[..., 0:7]`` (csrc/common.h slot_decode's order)."""
+    v = torch.zeros(W.shape[:-1], dtype=torch.float64)
+    for j in range(6, -1, -1):
+        v = v + torch.ldexp(W[..., j].to(torch.float64), torch.tensor(32 * j - 64))
+    return v
+
+
+def _davies_bouldin(S: torch.Tensor, cq: torch.Tensor) -> float:
+    """Mean over the clusters of max_{l != k} (S_k + S_l) / |c_k - c_l| in float64 (a zero
+    separation counts as +inf, scikit-learn's convention), the centre distances in row
+    blocks of <= 64 MB."""
+    Kn = cq.shape[0]
+    if Kn < 2:
+        return float("nan")
+    c = cq.to(torch.float64)
+    s = S.to(device=c.device, dtype=torch.float64)
+    rows = max(1, (1 << 26) // (8 * Kn))
+    total = torch.zeros((), dtype=torch.float64, device=c.device)
+    for i in range(0, Kn, rows):
+        M = torch.cdist(c[i : i + rows], c, compute_mode="donot_use_mm_for_euclid_dist")
+        R = (s[i : i + rows, None] + s[None, :]) / M
+        R = torch.where(M > 0, R, torch.zeros_like(R))     # (the diagonal too)
+        total = total + R.max(dim=1).values.sum()
+    return float(total / Kn)
+
+
+def quality_decode(table: torch.Tensor, centers: torch.Tensor, dtype: torch.dtype = torch.float32) -> dict:
+    """The cluster report of a quality table: float64 arithmetic in a fixed order on the host
+    (the centre distances of the Davies-Bouldin index on the centres' device).
+
+    Per cluster (CPU tensors ``[K]``): ``counts`` (int64, rows with a finite distance),
+    ``cluster_inertia`` (sum a^2), ``mean_distance`` (sum a / n_k), ``rms_distance``,
+    ``radius`` (the largest a), ``cluster_silhouette`` (mean simplified silhouette
+    1 - a / b over the cluster's rows) and ``n_nonfinite`` (int64, rows left out because their
+    distance is NaN or infinite); empty clusters get NaN means and radius 0.  Totals:
+    ``n_samples``, ``inertia`` (decoded from the digit words summed over the labels as
+    integers), ``silhouette`` (NaN for K = 1), ``balance`` and ``davies_bouldin`` (S =
+    ``mean_distance``, M = the distance between the centres as the kernels rank them; NaN
+    with fewer than two non-empty clusters)."""
+    from ..utils import metrics as mmetrics
+
+    T = table.detach().to("cpu")
+    K = T.shape[0]
+    counts = T[:, 7].clone()
+    nk = counts.to(torch.float64)
+    nan = torch.full((K,), float("nan"), dtype=torch.float64)
+    empty = counts == 0
+    inertia_k = _slot_value(T[:, 0:7])
+    suma = _slot_value(T[:, 8:15])
+    mean_d = torch.where(empty, nan, suma / nk)
+    rms = torch.where(empty, nan, (inertia_k / nk).sqrt())
+    sil_k = torch.where(empty | (K == 1), nan, T[:, 16].to(torch.float64) / nk / 2147483648.0)
+    radius = T[:, 17].to(torch.int32).view(torch.float32).to(torch.float64).sqrt()
+    n = int(counts.sum())
+    sil = float(T[:, 16].sum()) / n / 2147483648.0 if (K > 1 and n > 0) else float("nan")
+    full = (~empty).nonzero().flatten()
+    cq = cpu.quantize_centers(centers, dtype)
+    db = _davies_bouldin(mean_d[full], cq[full.to(cq.device)])
+    return {
+        "counts": counts, "cluster_inertia": inertia_k, "mean_distance": mean_d, "rms_distance": rms,
+        "radius": radius, "cluster_silhouette": sil_k, "n_nonfinite": T[:, 15].clone(),
+        "n_samples": n, "inertia": float(_slot_value(T[:, 0:7].sum(0))), "silhouette": sil,
+        "davies_bouldin": db, "balance": mmetrics.balance([int(c) for c in counts.tolist()]),
+    }
+
+
+def quality_rows(table: torch.Tensor, X: torch.Tensor, centers: torch.Tensor, *,
+                 pack: "CentroidPack | None" = None, block_rows: int | None = None) -> torch.Tensor:
+    """Accumulate the rows of ``X`` into ``table``: :func:`topk` with min(2, K) then
+    :func:`quality_accumulate`, in row blocks (``block_rows``, default 2^22), so the top-2
+    scratch stays bounded at any n.  The table does not depend on the block size."""
+    K = centers.shape[0]
+    block = int(block_rows) if block_rows else QUALITY_BLOCK_ROWS
+    if X.is_cuda and pack is None and X.shape[0] > block:   # pack the centres once for all blocks
+        X = pad_columns(X)
+        if dpad_for(X.shape[1], X.dtype):
+            pack = pack_centers(centers, X.shape[1], X.dtype, X.device)
+    for s in range(0, X.shape[0], block):
+        idx, d2 = topk(X[s : s + block], centers, min(2, K), pack=pack)
+        quality_accumulate(table, idx, d2)
+    return table
+
+
+def cluster_quality(X: torch.Tensor, centers: torch.Tensor, *, pack: "CentroidPack | None" = None,
+                    block_rows: int | None = None):
+    """Per-cluster quality of the rows of ``X`` under ``centers``: ``(report, table)``, the
+    report :func:`quality_decode`'s dict and the table the int64 ``[K, QUALITY_WORDS]``
+    reduction it was decoded from (on ``X``'s device)."""
+    table = torch.zeros((centers.shape[0], QUALITY_WORDS), dtype=torch.int64, device=X.device)
+    quality_rows(table, X, centers, pack=pack, block_rows=block_rows)
+    return quality_decode(table, centers, X.dtype), table
 
 
 def max_abs(X: torch.Tensor) -> float:

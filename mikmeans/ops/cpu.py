@@ -67,6 +67,65 @@ def topk(X: torch.Tensor, centers: torch.Tensor, m: int):
     return idx, d2
 
 
+QUALITY_WORDS = 24          # csrc/kernels.h QUALITY_WORDS
+_MASK32 = (1 << 32) - 1
+
+
+def _slot_digits(v: torch.Tensor):
+    """csrc/common.h slot_add on non-negative finite float64 values: ``(j0, d)`` with the
+    value truncated to a multiple of 2^-64 equal to sum_i d[i] * 2^(32 (j0 + i) - 64)
+    (three 32-bit digits, int64 [3, n]; all zero for v = 0)."""
+    bits = v.contiguous().view(torch.int64)
+    ex = (bits >> 52) & 0x7FF
+    m = (bits & ((1 << 52) - 1)) | torch.where(ex > 0, 1 << 52, 0)
+    s = torch.where(ex > 0, ex, torch.ones_like(ex)) - 1075 + 64
+    m = torch.where(s < 0, m >> (-s).clamp(0, 63), m)
+    s = s.clamp_min(0)
+    j0, o = s >> 5, s & 31
+    t0 = (m & _MASK32) << o                        # < 2^63
+    t1 = ((m >> 32) << o) + (t0 >> 32)
+    return j0, torch.stack([t0 & _MASK32, t1 & _MASK32, t1 >> 32])
+
+
+def quality_table(idx: torch.Tensor, d2: torch.Tensor, K: int) -> torch.Tensor:
+    """The per-cluster quality table int64 ``[K, QUALITY_WORDS]`` of a top-1 / top-2 result
+    (``idx`` int32, ``d2`` float32, both ``[n, 1 or 2]``): csrc/quality.hip in integer torch
+    arithmetic, word for word (its header has the layout).  The CPU path and the test oracle."""
+    if idx.dim() != 2 or idx.shape != d2.shape or idx.shape[1] not in (1, 2):
+        raise ValueError(f"quality_table needs idx and d2 of one shape [n, 1 or 2], got {tuple(idx.shape)}, "
+                         f"{tuple(d2.shape)}")
+    QW = QUALITY_WORDS
+    flat = torch.zeros(K * QW, dtype=torch.int64, device=idx.device)
+    mx = torch.zeros(K, dtype=torch.int64, device=idx.device)
+    for s0 in range(0, idx.shape[0], 1 << 20):
+        k = idx[s0 : s0 + (1 << 20), 0].to(torch.int64)
+        d = d2[s0 : s0 + (1 << 20)].to(torch.float32)
+        ok = (k >= 0) & (k < K)
+        k, d = k[ok], d[ok]
+        fin = torch.isfinite(d[:, 0])
+        flat.index_add_(0, k[~fin] * QW + 15, torch.ones_like(k[~fin]))
+        k, d = k[fin], d[fin]
+        a2f = d[:, 0].clamp_min(0.0) + 0.0            # (-0 -> +0)
+        a2 = a2f.to(torch.float64)
+        base = k * QW
+        flat.index_add_(0, base + 7, torch.ones_like(k))
+        for off, v in ((0, a2), (8, a2.sqrt())):
+            j0, dg = _slot_digits(v)
+            for i in range(3):
+                flat.index_add_(0, base + off + j0 + i, dg[i])
+        if d.shape[1] == 2:
+            b2f = d[:, 1]
+            b2 = b2f.to(torch.float64)
+            sv = (1.0 - (a2 / b2).sqrt()).clamp_min(0.0)
+            sv = torch.where(torch.isinf(b2f), torch.ones_like(sv), sv)
+            sv = torch.where(b2f > 0, sv, torch.zeros_like(sv))          # (a NaN or zero b^2: s = 0)
+            flat.index_add_(0, base + 16, torch.round(sv * 2147483648.0).to(torch.int64))
+        mx.scatter_reduce_(0, k, a2f.contiguous().view(torch.int32).to(torch.int64), "amax")
+    table = flat.view(K, QW)
+    table[:, 17] = mx
+    return table
+
+
 def cluster_sums(X: torch.Tensor, labels: torch.Tensor, K: int, weights=None):
     lab = labels.to(torch.int64)
     Xd = X.to(torch.float64)
