@@ -809,6 +809,424 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
   }
 }
 
+// Persistent form of the plain full bf16 pass with caller norms (the early-prologue path of
+// assign16_kernel, packed keys, 4 waves per ring, 2 ring slots): min(groups, resident
+// workgroups) workgroups take PTS-row groups -- the row blocks blockIdx.x names in the one-pass
+// grid -- from a group counter (a static stride left the workgroups whose waves share a SIMD
+// twice as long in the chunk loop to finish a third of the kernel after the others), so every group's seed offset, per-point-offset
+// decision, keys and slot addends are bitwise the one-pass kernel's.  A wave slot then never
+// sits in a prologue: after the last tile's MFMAs of a group are issued the fragment registers
+// are dead (the label epilogue reads best / bg / seg_best only), so the next group's norms and
+// fragments load into the SAME registers (no second fragment set: that spilled,
+// profiles/r4_04_persistent_grid_ab.md) and fly under the label epilogue, and the centre ring
+// never drains -- chunk 0 of the next pass goes out at the last chunk's barrier.
+// |c|^2 is re-sent to LDS per group behind the group-end barrier and the seed offset folded into
+// it as in the one-pass kernel (adding the offset per tile instead, on a pristine copy, cost
+// 4 VALU a tile: the SIMDs are bound by MFMA + VALU issue, not by waiting waves).
+// vmcnt order per wave and group: [chunk 0] [old labels] [norms] [P*NQ fragments] [epilogue
+// stores, slot atomics] [|c|^2]; the epilogue's wait for the old labels is counted on the norms
+// and fragments (the only younger operations that are issued unconditionally).
+// A kernel of its own, not a flag of assign16_kernel: the scope is one epilogue of that
+// kernel's five, and tests/test_isa_guard.py indexes assign16_kernel's template arguments.
+// Group counters of the persistent kernel, {next group - G, workgroups done}, zero between
+// launches; launches rotate through the slots, so launches in flight on different streams do
+// not share one.
+constexpr int PERSIST_CTR_SLOTS = 64;
+__device__ unsigned g_persist_ctr[PERSIST_CTR_SLOTS][2];
+
+template <int DPAD, int P, int OCC, int PMAJ>
+__global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a, int ngroups, int cslot) {
+  using T = uint16_t;
+  using C = Assign16Cfg<T, DPAD, P, 0, 2, 4>;
+  constexpr int EJ = (C::P + 3) / 4;
+  static_assert(C::P * C::NQ + EJ < 64, "vmcnt range");
+  static_assert(EJ == 1, "one norm and one old label per lane");
+  static_assert(DPAD <= 256, "narrow rows");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int cn_bytes = ((a.Kpad * 4 + 1023) / 1024) * 1024;
+  char* cn_lds = smem;
+  char* bufs = smem + cn_bytes;
+  const int ncl = a.Kpad / (16 * C::CT);
+  const uint32_t loff = (uint32_t)lane * 16u;
+  const __amdgpu_buffer_rsrc_t rC = make_rsrc(a.Cpack, (uint32_t)a.Kpad * DPAD * sizeof(T));
+  auto issue_chunk = [&](int c, int slot) {
+    const uint32_t src = (uint32_t)c * C::CHUNK_BYTES;
+    char* dst = bufs + slot * C::CHUNK_BYTES;
+#pragma unroll
+    for (int i = 0; i < C::NPW; ++i) {
+      const int pc = wid + i * C::NW;
+      blds16(rC, (MK_LDS void*)(dst + pc * 1024), loff, src + (uint32_t)pc * 1024u);
+    }
+  };
+  const int64_t N = a.N;
+  // (the LDS layout of assign16_kernel: min / max scratch, per-point offsets, wave totals)
+  float* red = (float*)(bufs + C::NBUF * C::CHUNK_BYTES);
+  float* opt = (float*)(bufs + C::NBUF * C::CHUNK_BYTES + 16 * C::NW);
+  double* wacc = (double*)(bufs + C::NBUF * C::CHUNK_BYTES + 16 * C::NW + C::OPT_BYTES);
+  // one norm (the gathered-norm half of the offsets area, unused with caller norms) and one old
+  // label (PERSIST_LDS_EXTRA bytes behind the wave totals) per thread, landed by LDS-DMA
+  uint32_t* xg_lds = (uint32_t*)(opt + C::NW * 16 * C::PP);
+  uint32_t* el_lds = (uint32_t*)(bufs + C::NBUF * C::CHUNK_BYTES + 16 * C::NW + C::OPT_BYTES + 16 * C::NW);
+  const unsigned kmask = key6_mask();
+  const int G = (int)gridDim.x;
+  int grp = (int)blockIdx.x;   // the first group; the others come from the launch's group counter
+  unsigned* ctr = g_persist_ctr[cslot];
+  int* nxt_lds = (int*)(red + 2 * C::NW);   // the next group, handed from thread 0 to the workgroup
+  int s0 = 0;   // ring slot of this pass's chunk 0 (alternates when a pass has an odd chunk count)
+
+  // A lane's part of every row, norm and label address is one 32-bit offset inside the group
+  // on a scalar base (the group's first row), so no 64-bit VGPR address lives across the
+  // chunk loop.
+  const uint32_t rowb = (uint32_t)a.ldx * (uint32_t)sizeof(T);
+  auto rows_of = [&](int gi) -> int {   // valid rows of group gi
+    const int64_t left = N - (int64_t)gi * C::PTS;
+    return left < C::PTS ? (int)left : C::PTS;
+  };
+  // (group addresses are rebuilt from a laundered thread id where they are used: as loop
+  // invariants the compiler hoisted them all out of the group loop and spilled them)
+  auto fresh_tid = []() -> int {
+    int t = (int)threadIdx.x;
+    asm volatile("" : "+v"(t));
+    return t;
+  };
+  // lane ^ o shuffles on a laundered lane id (the library forms' addresses are loop invariants too)
+  auto sx = [](int ln, int v, int o) -> int { return __builtin_amdgcn_ds_bpermute((ln ^ o) << 2, v); };
+  auto sxf = [&](int ln, float v, int o) -> float { return __int_as_float(sx(ln, __float_as_int(v), o)); };
+  auto lrow_of = [&](int tid, int p) -> int { return wid * (C::P * 16) + p * 16 + (tid & 15); };   // row in the group
+
+  // The prefetched fragment loads are inline asm, tied to the registers that hold the current
+  // fragments ("+v"): as compiler-visible loads the next group's fragments were given registers
+  // of their own and spilled.  The compiler's wait-count pass does not see asm loads: the wait
+  // before the group's first MFMA is this kernel's (the chunk loop's vmcnt(0)), and the waits
+  // the compiler inserts for its own operations only get stricter (vmcnt retires in order).
+  // Nothing else may touch those registers while a load is in flight -- no copy, no spill:
+  // tests/test_isa_persist.py reads the code object for that.  The norms and the old labels
+  // cross the group boundary through LDS (dword LDS-DMA), not in registers, for that reason:
+  // a register-carried value the compiler was free to copy before it had landed.
+  auto ld128 = [](u32x4& d, uint32_t vo, const void* base) {
+    asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(d) : "v"(vo), "s"(base) : "memory");
+  };
+  auto blds4 = [](__amdgpu_buffer_rsrc_t rs, MK_LDS void* lds_base, uint32_t voff) {   // lane i -> lds_base + 4 i
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lds_base, 4, voff, 0, 0, 0);
+  };
+
+  u32x4 xr[C::P][C::NQ];
+#pragma unroll
+  for (int p = 0; p < C::P; ++p)
+#pragma unroll
+    for (int q = 0; q < C::NQ; ++q) xr[p][q] = u32x4{0u, 0u, 0u, 0u};
+  // norms, |c|^2 and fragments of group gi, rows clamped to the group's last (a group past the
+  // last: the last group's loads go out again, so the waits count the same on every path;
+  // nothing reads them)
+  auto load_group = [&](int gi) {
+    gi = gi < ngroups ? gi : ngroups - 1;
+    const int nv = rows_of(gi);
+    const int64_t gb = (int64_t)gi * C::PTS;
+    const char* xb = (const char*)a.X + gb * (int64_t)rowb;
+    // lane (r, g): the norm of its epilogue rows, block p = g (descriptor: the group's valid rows)
+    const __amdgpu_buffer_rsrc_t rXn = make_rsrc(a.xn + gb, (uint32_t)nv * 4u);
+    __builtin_amdgcn_sched_barrier(0);
+    const int tid = fresh_tid();
+    const int gg = (tid & 63) >> 4;
+    blds4(rXn, (MK_LDS void*)(xg_lds + wid * 64), (uint32_t)min(lrow_of(tid, gg < C::P ? gg : C::P - 1), nv - 1) * 4u);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int p = 0; p < C::P; ++p) {
+      const uint32_t vo = (uint32_t)min(lrow_of(tid, p), nv - 1) * rowb + (uint32_t)gg * 16u;
+#pragma unroll
+      for (int q = 0; q < C::NQ; ++q) ld128(xr[p][q], vo + (uint32_t)q * 64u, xb);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  if (a.timeline && threadIdx.x == 0) {
+    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+    a.timeline[(int64_t)grp * 8] = t;
+    a.timeline[(int64_t)grp * 8 + 7] = t;
+  }
+  // |c|^2 by LDS-DMA: the seed offset is folded into the LDS copy per group, so every group
+  // starts from a fresh copy (4 KiB at K = 1024; a pristine second copy does not fit the LDS
+  // of four workgroups)
+  auto issue_cn = [&]() {
+    const __amdgpu_buffer_rsrc_t rN = make_rsrc(a.cn, (uint32_t)a.Kpad * 4u);
+    for (int pc = wid; pc < cn_bytes / 1024; pc += C::NW)
+      blds16(rN, (MK_LDS void*)(cn_lds + pc * 1024), loff, (uint32_t)pc * 1024u);
+  };
+  issue_cn();
+  issue_chunk(0, 0);
+  load_group(grp);
+  for (;;) {
+    const int nvc = rows_of(grp);   // this group's valid rows
+    int nxt = 0;            // the group after this one (>= ngroups: none), known from the last chunk on
+    bool has_next = false;
+    // this group's norms and this wave's pieces of |c|^2 landed (the youngest operations: the
+    // fragments, issued a whole label epilogue earlier, and the epilogue's stores retire with
+    // them -- a stalled wave costs little here, the SIMD is kept busy by the other three)
+    wait_vmcnt<0>();
+    // (timeline: the stamps are stored as they are taken, none is carried in registers; word 0,
+    // entry, is the previous group's exit, and word 7 repeats it: the group's loads were issued
+    // under the previous group's epilogue)
+    if (a.timeline && threadIdx.x == 0) a.timeline[(int64_t)grp * 8 + 6] = __builtin_amdgcn_s_memrealtime();
+    float exn[EJ];   // the epilogue's norms (xg takes the next group's under the epilogue)
+    exn[0] = __uint_as_float(xg_lds[fresh_tid()]);   // (this wave's own DMA, retired by the wait above)
+    // seed offset, or per-point offsets, of this group (see assign16_kernel)
+    float off = 0.f;
+    bool ppo = false;
+    unsigned fetched;
+    {
+      const int ttid = fresh_tid();
+      fetched = 0u;
+      const int tln = ttid & 63, tr = ttid & 15, tg = tln >> 4;
+      float m = 0.f, mn = 3.0e38f;
+#pragma unroll
+      for (int j = 0; j < EJ; ++j) { m = fmaxf(m, exn[j]); mn = fminf(mn, exn[j]); }
+      m = fmaxf(m, sxf(tln, m, 16));
+      mn = fminf(mn, sxf(tln, mn, 16));
+      m = fmaxf(m, sxf(tln, m, 32));
+      mn = fminf(mn, sxf(tln, mn, 32));
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        m = fmaxf(m, sxf(tln, m, o));
+        mn = fminf(mn, sxf(tln, mn, o));
+      }
+      if (tln == 0) { red[2 * wid] = m; red[2 * wid + 1] = mn; }
+      // every wave is past the previous group's chunk loop and label epilogue here: |c|^2,
+      // the offsets and the wave totals in LDS may be rewritten behind this barrier
+      wait_lgkm0();
+      raw_barrier();
+      float mnw = 3.0e38f;
+#pragma unroll
+      for (int w = 0; w < C::NW; ++w) { off = fmaxf(off, red[2 * w]); mnw = fminf(mnw, red[2 * w + 1]); }
+      ppo = __builtin_amdgcn_readfirstlane((int)(off > 4.f * mnw)) != 0;
+      // the next group: one returning atomic per group, a whole chunk loop ahead of its use
+      if (ttid == 0) fetched = atomicAdd(ctr, 1u);
+      if (!ppo) {
+        off = __builtin_fmaf(off, 2.44140625e-04f, off);  // * (1 + 2^-12)
+        off = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(off)));
+        // (every wave's |c|^2 pieces landed before the barrier above)
+        for (int kk = ttid; kk < a.Kpad; kk += C::NW * 64) ((float*)cn_lds)[kk] += off;
+      } else {
+        off = 0.f;
+#pragma unroll
+        for (int j = 0; j < EJ; ++j)
+          if (4 * j + tg < C::P) opt[(wid * 16 + tr) * C::PP + 4 * j + tg] = __builtin_fmaf(exn[j], 2.44140625e-04f, exn[j]);
+      }
+    }
+
+    float best[C::P], seg_best[C::P];
+    int bg[C::P];
+#pragma unroll
+    for (int p = 0; p < C::P; ++p) { best[p] = 3.0e38f; seg_best[p] = 3.0e38f; bg[p] = 0; }
+
+    // A chunk's barrier and ring refill; the pass's last chunk sends chunk 0 of the next pass
+    // (the centres are the same every pass, so the ring never drains) and the label epilogue's
+    // old labels, one chunk ahead of their use.
+    auto chunk_head = [&](int c, auto last_tag) -> const char* {
+      // chunk c landed (c = 0: and this group's fragments; the previous epilogue's stores are
+      // the only younger operations, their number varies on a ragged tail)
+      wait_vmcnt<0>();
+      if constexpr (decltype(last_tag)::value) {
+        if (fresh_tid() == 0) *nxt_lds = G + (int)fetched;   // (the atomic returned: the wait above)
+      }
+      wait_lgkm0();
+      raw_barrier();  // RAW for chunk c, WAR for the slot refilled next (read at c-1)
+      if constexpr (!decltype(last_tag)::value) {
+        issue_chunk(c + 1, (s0 + c + 1) & 1);
+      } else {
+        nxt = __builtin_amdgcn_readfirstlane(*nxt_lds);
+        has_next = nxt < ngroups;
+        if (has_next) issue_chunk(0, (s0 + c + 1) & 1);
+        const int tid = fresh_tid();
+        const __amdgpu_buffer_rsrc_t rLo = make_rsrc(a.labels + (int64_t)grp * C::PTS, (uint32_t)nvc * 4u);
+        blds4(rLo, (MK_LDS void*)(el_lds + wid * 64), (uint32_t)min(lrow_of(tid, (tid & 63) >> 4), nvc - 1) * 4u);
+      }
+      return bufs + ((s0 + c) & 1) * C::CHUNK_BYTES;
+    };
+    // One tile.  PPO: 0 / 1 = without / with per-point offsets (two copies of the chunk loop, as
+    // in assign16_kernel), 2 = decided at run time -- the pass's very last tile (FINAL), a single
+    // copy, so the next group's loads stand once, in straight-line code right after the pass's
+    // last MFMAs (in both copies of the loop, or under a branch of a shared body, the compiler
+    // kept two fragment sets alive and spilled).
+    auto run_tile = [&](int c, int tl_i, const char* buf, auto ppo_tag, auto final_tag) {
+      constexpr int PPO = decltype(ppo_tag)::value;
+      constexpr bool FINAL = decltype(final_tag)::value;
+      const int tile = c * C::CT + tl_i;
+      u32x4 aw[C::NQ];
+      const f32x4 ci = *(const f32x4*)(cn_lds + (tile * 16 + 4 * g) * 4);
+      const char* tl = buf + tl_i * C::TILE_BYTES + lane * 16;
+#pragma unroll
+      for (int q = 0; q < C::NQ; ++q) aw[q] = *(const u32x4*)(tl + q * 1024);
+      f32x4 acc[C::P];
+#pragma unroll
+      for (int p = 0; p < C::P; ++p) acc[p] = ci;
+      if (PPO == 1 || (PPO == 2 && ppo)) {  // (added BEFORE the MFMAs, see assign16_kernel)
+        const float* o = opt + (wid * 16 + r) * C::PP;
+#pragma unroll
+        for (int p4 = 0; p4 < C::P; p4 += 4) {
+          const f32x4 ov = *(const f32x4*)(o + p4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (p4 + j < C::P) seed_add(acc[p4 + j], ov[j]);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_sched_barrier(0);
+      unsigned t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+      const unsigned tis = (unsigned)(tile & 15) << 2;
+      asm volatile("s_mov_b32 %0, %4\n\ts_or_b32 %1, %4, 1\n\ts_or_b32 %2, %4, 2\n\ts_or_b32 %3, %4, 3"
+                   : "=s"(t0), "=s"(t1), "=s"(t2), "=s"(t3) : "s"(tis) : "scc");
+      if constexpr (PMAJ) {
+#pragma unroll
+        for (int p = 0; p < C::P; ++p) {
+#pragma unroll
+          for (int q = 0; q < C::NQ; ++q) {
+            acc[p] = Mfma16<T>::run(aw[q], xr[p][q], acc[p]);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < C::NQ; ++q) {
+#pragma unroll
+          for (int p = 0; p < C::P; ++p) acc[p] = Mfma16<T>::run(aw[q], xr[p][q], acc[p]);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
+      // the pass's last MFMAs are issued: the fragment registers take the next group's rows
+      if constexpr (FINAL) load_group(nxt);
+#pragma unroll
+      for (int p = 0; p < C::P; ++p) {
+        const f32x4& sv = acc[p];
+        const float k0 = pack_key6(sv[0], kmask, t0), k1 = pack_key6(sv[1], kmask, t1);
+        const float k2 = pack_key6(sv[2], kmask, t2), k3 = pack_key6(sv[3], kmask, t3);
+        seg_best[p] = min3f(min3f(k0, k1, k2), k3, seg_best[p]);
+      }
+      if (FINAL || (tile & 15) == 15) {
+#pragma unroll
+        for (int p = 0; p < C::P; ++p) {
+          const float sv = __uint_as_float(__float_as_uint(seg_best[p]) & ~63u);
+          const float bv = __uint_as_float(__float_as_uint(best[p]) & ~63u);
+          if (sv < bv) { best[p] = seg_best[p]; bg[p] = tile >> 4; }
+          seg_best[p] = 3.0e38f;
+        }
+      }
+    };
+    auto chunk_loop = [&](auto ppo_tag) {
+      for (int c = 0; c + 1 < ncl; ++c) {
+        const char* buf = chunk_head(c, std::false_type{});
+#pragma unroll
+        for (int tl_i = 0; tl_i < C::CT; ++tl_i) run_tile(c, tl_i, buf, ppo_tag, std::false_type{});
+      }
+      const char* buf = chunk_head(ncl - 1, std::true_type{});
+#pragma unroll
+      for (int tl_i = 0; tl_i + 1 < C::CT; ++tl_i) run_tile(ncl - 1, tl_i, buf, ppo_tag, std::false_type{});
+    };
+    if (a.timeline && threadIdx.x == 0) a.timeline[(int64_t)grp * 8 + 1] = __builtin_amdgcn_s_memrealtime();
+    if (ppo) chunk_loop(std::integral_constant<int, 1>{});
+    else chunk_loop(std::integral_constant<int, 0>{});
+    run_tile(ncl - 1, C::CT - 1, bufs + ((s0 + ncl - 1) & 1) * C::CHUNK_BYTES, std::integral_constant<int, 2>{},
+             std::true_type{});
+    if (a.timeline && threadIdx.x == 0) {
+      unsigned long long* tl = a.timeline + (int64_t)grp * 8;
+      tl[2] = __builtin_amdgcn_s_memrealtime();
+      tl[4] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_ID
+      tl[5] = (unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));   // XCC_ID
+    }
+
+    // The group's label epilogue: assign16_kernel's, packed keys with caller norms
+    float inert = 0.f;
+    int changed = 0;
+    // the old labels landed: younger are the next group's norms and fragments
+    wait_vmcnt<EJ + C::P * C::NQ>();
+    const int etid = fresh_tid();
+    const int eold = (int)el_lds[etid];
+    const int eln = etid & 63, er = etid & 15, eg = eln >> 4;
+    // (descriptors over the group's valid rows: no store can leave them)
+    const __amdgpu_buffer_rsrc_t rL = make_rsrc(a.labels + (int64_t)grp * C::PTS, (uint32_t)nvc * 4u);
+    const __amdgpu_buffer_rsrc_t rM = make_rsrc(a.mind ? a.mind + (int64_t)grp * C::PTS : nullptr,
+                                                a.mind ? (uint32_t)nvc * 4u : 0u);
+#pragma unroll
+    for (int p = 0; p < C::P; ++p) {
+      const unsigned bits = __float_as_uint(best[p]);
+      const int idx = (int)(bits & 63u);
+      int k = (bg[p] * 16 + (idx >> 2)) * 16 + 4 * eg + (idx & 3);
+      float v = __uint_as_float(bits & ~63u);
+#pragma unroll
+      for (int o = 16; o <= 32; o <<= 1) {
+        const float vo = sxf(eln, v, o);
+        const int ko = sx(eln, k, o);
+        if (vo < v || (vo == v && ko < k)) { v = vo; k = ko; }
+      }
+      const int lr = lrow_of(etid, p);
+      if ((p & 3) == eg && lr < nvc) {
+        const float offp = ppo ? opt[(wid * 16 + er) * C::PP + p] : off;
+        v -= offp;   // back to |c|^2 - 2 x.c
+        if (a.track_changed) changed += (eold != k);
+        __builtin_amdgcn_raw_buffer_store_b32((unsigned)k, rL, (uint32_t)lr * 4u, 0, 0);
+        const float d = fmaxf(exn[0] + v, 0.f);
+        inert += d;
+        if (a.mind) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d), rM, (uint32_t)lr * 4u, 0, 0);
+      }
+    }
+    if (a.slots) {   // the wave's totals, in its LDS slot
+      // (wave_sum's butterflies, common.h)
+      double di = (double)inert;
+      int dc = changed;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const long long b = __double_as_longlong(di);
+        const int lo = sx(eln, (int)(unsigned)b, o), hi = sx(eln, (int)(b >> 32), o);
+        di += __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+        dc += sx(eln, dc, o);
+      }
+      if (eln == 0) {
+        wacc[2 * wid] = di;
+        wacc[2 * wid + 1] = (double)dc;
+      }
+    }
+    if (a.timeline && threadIdx.x == 0) {
+      const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+      a.timeline[(int64_t)grp * 8 + 3] = t;
+      if (has_next) {
+        a.timeline[(int64_t)nxt * 8] = t;
+        a.timeline[(int64_t)nxt * 8 + 7] = t;
+      }
+    }
+    // group end: the wave totals are published and every wave is past its last read of |c|^2
+    // (raw barrier: the label / distance stores and the next group's loads stay in flight)
+    wait_lgkm0();
+    raw_barrier();
+    if (has_next) issue_cn();
+    if (a.slots) {
+      // one slot_add per group, the one-pass workgroup's addends and slot
+      if (threadIdx.x == 0) {
+        double si = 0, sc = 0;
+#pragma unroll
+        for (int w = 0; w < C::NW; ++w) { si += wacc[2 * w]; sc += wacc[2 * w + 1]; }
+        slot_add((unsigned long long*)(a.slots + (grp % NSLOT) * SLOT_STRIDE), si, (long long)sc);
+      }
+    }
+    if (!has_next) break;
+    grp = nxt;
+    s0 = (s0 + ncl) & 1;
+  }
+  // the last group's prefetch (a repeat of the last group's rows, nothing reads it) may still
+  // be in flight into the fragment registers, which the code below is free to reuse
+  wait_vmcnt<0>();
+  // every workgroup arrives here after its last fetch: the last one resets the counter pair,
+  // inside the launch, so a captured graph replays without a host-side reset
+  if (threadIdx.x == 0 && atomicAdd(ctr + 1, 1u) == (unsigned)G - 1u) {
+    atomicExch(ctr, 0u);
+    atomicExch(ctr + 1, 0u);
+  }
+}
+
 // Centre-split epilogue: labels, squared distances, inertia and changed count from the
 // per-point minimum key the splits left; resets every key for the next call.
 __global__ __launch_bounds__(256) void split_finish_kernel(AssignArgs a) {
@@ -930,6 +1348,53 @@ static void launch16_k(const AssignArgs& b, const dim3& grid, size_t lds, hipStr
   }
 }
 
+// The persistent kernel's grid: min(groups, workgroups resident at once) -- the occupancy of
+// this instantiation at this LDS size times the device's CUs, both queried once and cached --
+// or `cap` workgroups (tests: several groups per workgroup at small N).
+template <int DPAD, int P, int OCC, int PMAJ>
+static hipError_t launch16_persist(const AssignArgs& b, int64_t nblk, size_t lds, int cap, hipStream_t s) {
+  const void* fn = (const void*)assign16_persist_kernel<DPAD, P, OCC, PMAJ>;
+  static size_t occ_lds = 0;
+  static int occ_blocks = 0;
+  static int cus[64] = {};
+  if (!occ_blocks || occ_lds != lds) {
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    int nb = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, lds);
+    if (e != hipSuccess) return e;
+    if (nb < 1) return hipErrorInvalidValue;
+    occ_blocks = nb;
+    occ_lds = lds;
+  }
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64) return hipErrorInvalidValue;
+  if (!cus[dev]) {
+    e = hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev);
+    if (e != hipSuccess) return e;
+    if (cus[dev] < 1) return hipErrorInvalidValue;
+  }
+  int64_t grid = (int64_t)occ_blocks * cus[dev];
+  if (cap > 0 && cap < grid) grid = cap;
+  if (nblk < grid) grid = nblk;
+  static int cslot = 0;
+  cslot = (cslot + 1) % PERSIST_CTR_SLOTS;
+  hipLaunchKernelGGL((assign16_persist_kernel<DPAD, P, OCC, PMAJ>), dim3((unsigned)grid), dim3(256), lds, s, b,
+                     (int)nblk, cslot);
+  return hipGetLastError();
+}
+
+// Where the persistent kernel runs by default: the shape whose one-process A/B against the
+// one-pass grid it won -- bf16 D=128 K=1024 at N=1e8, 18.18 against 18.67 ms (+2.6 %, 11
+// interleaved rounds; at N=2e7 +0.3 %, inside the noise: the ~40 us a launch's slowest
+// workgroups finish after the rest weigh more on a 3.7 ms kernel) -- so from 5e7 rows up
+// (profiles/r7_01_persistent_assign.md).  V_ASSIGN_PERSIST = 0 / 1 forces it off / on wherever
+// it applies, >= 2 also caps its grid to that many workgroups (tests).
+constexpr size_t PERSIST_LDS_EXTRA = 1024;      // one old label per thread
+constexpr int PERSIST_KPAD = 1024;
+constexpr int64_t PERSIST_MIN_GROUPS = 196608;
+
 template <typename T, int DPAD, int P, int CT_ = 0, int NBUF_ = 2, int OCC = 1, int NW_ = 4>
 static hipError_t launch16_t(const AssignArgs& a, hipStream_t s) {
   using C = Assign16Cfg<T, DPAD, P, CT_, NBUF_, NW_>;
@@ -949,6 +1414,19 @@ static hipError_t launch16_t(const AssignArgs& a, hipStream_t s) {
   if (g_timeline && nblk <= g_timeline_cap && splits == 1) b.timeline = g_timeline;
   b.epi_prefetch = variant(V_ASSIGN_EPI) != 0;
   b.early_prologue = variant(V_ASSIGN_EARLY) != 0;
+  // Plain full bf16 passes with caller norms at the headline geometry (the conditions of the
+  // one-pass kernel's early prologue, no device row count, point-block-major issue): the
+  // persistent kernel (default: see PERSIST_MIN_GROUPS).
+  if constexpr (sizeof(T) == 2 && DPAD == 128 && P == 4 && CT_ == chunk_tiles16(2, 128) && NBUF_ == 2 && OCC == 4 &&
+                NW_ == 4) {
+    const int pv = variant(V_ASSIGN_PERSIST);
+    const int pm = variant(V_ASSIGN_PMAJ);
+    const bool applies = b.xn && !b.rows && !b.oseed && !b.split_keys && !b.n_dev && !b.ub && b.epi_prefetch &&
+                         b.early_prologue && b.D == DPAD && (pm < 0 || pm == 1);
+    const bool dflt = b.Kpad == PERSIST_KPAD && nblk >= PERSIST_MIN_GROUPS;
+    if (applies && lds + PERSIST_LDS_EXTRA <= 160 * 1024 && (pv >= 0 ? pv != 0 : dflt))
+      return launch16_persist<DPAD, P, OCC, 1>(b, nblk, lds + PERSIST_LDS_EXTRA, pv >= 2 ? pv : 0, s);
+  }
   bool varg = false;
   constexpr bool VARG_OK = sizeof(T) == 2 && DPAD <= 64;   // D=128: -12 % at K=1024, -4 % at 2048 (r3_11)
   if constexpr (VARG_OK) {

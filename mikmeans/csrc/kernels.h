@@ -32,10 +32,13 @@ constexpr int SLOT_STRIDE = 8;
 // environment: the values are taken from MIKMEANS_<NAME> once when the extension loads and
 // changed only through set_variant (mikmeans.ops.native.variant); -1 = the built-in rule.
 // A captured hipGraph keeps the geometry that was in force when it was recorded.
-// (Round 6 removed the measured losers: the persistent grid, the centre-stationary kernel, the
-// first-wave stagger and the prologue priority; their results stay in profiles/.)
+// (Round 6 removed the measured losers: the persistent grid with a second fragment set, the
+// centre-stationary kernel, the first-wave stagger and the prologue priority; their results
+// stay in profiles/.)
+// V_ASSIGN_PERSIST: 0 = the one-pass grid, 1 = the persistent kernel wherever it applies (plain
+// full bf16 D=128 passes with caller norms), n >= 2 = on a grid of n workgroups (tests).
 enum Variant { V_ASSIGN_VARG = 0, V_ASSIGN_PMAJ, V_ASSIGN_GEOM, V_UPDATE_KS, V_UPDATE_KS_GM, V_BLOBS_TPR,
-               V_ASSIGN_TOP2_GEOM, V_ASSIGN_EPI, V_ASSIGN_EARLY, V_COLSTAT_BLOCKS, V_COUNT };
+               V_ASSIGN_TOP2_GEOM, V_ASSIGN_EPI, V_ASSIGN_EARLY, V_COLSTAT_BLOCKS, V_ASSIGN_PERSIST, V_COUNT };
 int variant(Variant v);
 void set_variant(Variant v, int value);
 

@@ -115,6 +115,7 @@ def main():
     for n in names:
         med = statistics.median(times[n])
         res[n] = {"median_ms": round(med, 4), "min_ms": round(min(times[n]), 4),
+                  "spread_ms": round(max(times[n]) - min(times[n]), 4),   # over the rounds' timings
                   "tflops": round(2.0 * m * a.k * a.d / (med * 1e-3) / 1e12, 1),
                   "labels_equal": bool(torch.equal(labels[n], ref))}
         if clocks[n]:
