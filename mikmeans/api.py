@@ -197,6 +197,37 @@ def _report_table(centers, comm, dtype, fold) -> ClusterReport:
     return ClusterReport.from_table(table, centers, dtype)
 
 
+def _exemplar_lists(K: int, m: int, device, comm, n_local: int, farthest: bool, squared: bool, fold):
+    """``fold(table)`` min-inserts this rank's rows (indexed from 0) into an empty exemplar
+    table; the lists are then merged over the ranks of ``comm`` -- every rank's ``[K, m]``
+    (key word, global row) pairs all-gathered, the m lexicographically smallest kept per
+    cluster -- and decoded: ``(rows int64 [K, m], distances float32 [K, m])``, the same on every
+    rank and bit for bit the one-rank result on the concatenated shards."""
+    from . import ops
+
+    if int(n_local) >= 1 << 32:
+        raise ValueError(f"cluster_exemplars takes fewer than 2^32 rows in one call, got {int(n_local)}")
+    table = ops.exemplar_new(K, m, device)
+    fold(table)
+    if comm is not None and comm.grouped:
+        _, start = _shard_info(int(n_local), comm, device)
+        rows, _ = ops.exemplar_decode(table, row_start=start)
+        last = 1 << 62                                        # (past every key word: they are below 2^31)
+        hi = torch.where(rows < 0, last, table >> 32)
+        W = comm.world
+        hi = comm.all_gather(hi).permute(1, 0, 2).reshape(K, W * m)
+        rows = comm.all_gather(rows).permute(1, 0, 2).reshape(K, W * m)
+        o = torch.argsort(rows, dim=1, stable=True)           # by the global row, then (stable) by the key
+        hi, rows = hi.gather(1, o), rows.gather(1, o)         # word: the pairs in lexicographic order
+        o = torch.argsort(hi, dim=1, stable=True)[:, :m]
+        hi, rows = hi.gather(1, o), rows.gather(1, o)
+        bits = torch.where(rows < 0, 0, (0x7F7FFFFF - hi) if farthest else hi)
+        d2 = torch.where(rows < 0, float("nan"), bits.to(torch.int32).view(torch.float32))
+    else:
+        rows, d2 = ops.exemplar_decode(table, farthest=farthest)
+    return rows, (d2 if squared else d2.sqrt())
+
+
 class _Params:
     """scikit-learn estimator protocol: ``get_params`` / ``set_params`` over the constructor's
     keyword arguments (so ``sklearn.base.clone``, pipelines and grid searches can rebuild an
@@ -381,6 +412,47 @@ class _Serving(_Params):
 
         rep = _report_table(c, getattr(self, "comm", None) or get_comm(), self.dtype, fold)
         return rep if torch.is_tensor(X) else rep.numpy()
+
+    def cluster_exemplars(self, X, m: int, *, farthest: bool = False, squared: bool = False,
+                          block_rows: int | None = None):
+        """For every cluster the ``m`` rows of ``X`` assigned to it that lie nearest its centre
+        (``farthest``: the ``m`` farthest): ``(rows [K, m] int64, distances [K, m] float32)``.
+        Nearest lists are in ascending, farthest lists in descending order of distance, equal
+        distances by the lower row index; a cluster with fewer than ``m`` rows is padded with row
+        -1 and distance NaN.  ``m`` counts rows, not centres: 1 <= m <= 64, and it may exceed
+        ``n_clusters``.  Distances are Euclidean as in :meth:`transform` / :meth:`predict_topk`
+        (``squared``: the kernel's squared values; cosine models work on unit rows).
+
+        One pass over ``X`` and no sort of its rows: the top-1 kernel (:meth:`predict_topk`'s, on
+        the serving pack) gives each row's centre and squared distance, and csrc/exemplars.hip
+        min-inserts (distance bits, row) keys into an integer ``[K, m]`` table with 64-bit atomic
+        min.  The result is bitwise the same from run to run and for any ``block_rows`` (rows per
+        top-1 pass; host rows bound for a GPU model are also copied in blocks of that size).  In
+        a multi-rank job ``X`` is the rank's shard, the row index is the global one (shard start
+        + local index) and every rank returns the same lists: those of a one-rank call on the
+        concatenated shards.  One call takes fewer than 2^32 rows.
+
+        A row's cluster and distance are :meth:`predict_topk`'s first column: the exact nearest
+        centre, the lower index on ties, as in :meth:`cluster_report`.  For bfloat16 that can
+        differ from :meth:`predict` on near-ties, which ranks by packed keys.  Rows whose
+        distance is NaN or infinite are in no list.  numpy in, numpy out."""
+        from . import ops
+
+        self._check_fitted()
+        c = self.cluster_centers_
+
+        def fold(table):
+            seen = [0]
+
+            def run(Xt, pk):
+                ops.exemplar_rows(table, Xt, c, row0=seen[0], farthest=farthest, pack=pk, block_rows=block_rows)
+                seen[0] += Xt.shape[0]
+
+            self._fold_blocks(X, run, block_rows)
+
+        rows, d = _exemplar_lists(c.shape[0], m, c.device, getattr(self, "comm", None) or get_comm(),
+                                  X.shape[0], farthest, squared, fold)
+        return (rows, d) if torch.is_tensor(X) else (rows.cpu().numpy(), d.cpu().numpy())
 
     def transform(self, X):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine
@@ -1210,6 +1282,23 @@ def cluster_report(X, centers, dtype="float32") -> ClusterReport:
     c = c.to(dev)
     rep = _report_table(c, get_comm(), dt, lambda table: ops.quality_rows(table, Xt, c))
     return rep.numpy() if was_numpy else rep
+
+
+def cluster_exemplars(X, centers, m: int, dtype="float32", farthest: bool = False):
+    """For each of the given ``centers`` the ``m`` rows of ``X`` nearest it (``farthest``: farthest
+    from it) among the rows assigned to it: ``(rows [K, m], Euclidean distances [K, m])``
+    (``KMeans.cluster_exemplars`` without a model; with a process group ``X`` is the rank's shard
+    and the rows are global indices)."""
+    from . import ops
+
+    was_numpy = not torch.is_tensor(X)
+    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
+    dev = c.device if torch.is_tensor(centers) else _default_device(None)
+    Xt, _ = _to_tensor(X, dev, resolve_dtype(dtype))
+    c = c.to(dev)
+    rows, d = _exemplar_lists(c.shape[0], m, dev, get_comm(), Xt.shape[0], farthest, False,
+                              lambda table: ops.exemplar_rows(table, Xt, c, farthest=farthest))
+    return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
 
 
 def fit_predict(X, k: int, **kw):

@@ -6,7 +6,8 @@ Commands (the reference's top-bar controls, app.mjs:240-288, as a CLI):
                   checkpoint (safetensors + JSON), the flat-float ``centroids.json`` and labels
 * ``predict``  -- labels of a dataset under a saved model
 * ``report``   -- per-cluster quality of a dataset under a saved model (sizes, inertia, radius,
-                  simplified silhouette, Davies-Bouldin), as JSON
+                  simplified silhouette, Davies-Bouldin), as JSON; ``--exemplars M`` adds every
+                  cluster's M nearest (``--farthest``: farthest) rows
 * ``blobs``    -- write a synthetic Gaussian-blob dataset
 * ``room``     -- the trait-card game headless: seed/populate/auto-assign/dashboard/export/import
 * ``session``  -- one participant of a live, replicated room session: found it (hosting the
@@ -136,14 +137,24 @@ def cmd_predict(a) -> int:
 
 def cmd_report(a) -> int:
     """Per-cluster quality of a dataset under a saved model (``KMeans.cluster_report``): every
-    rank folds its shard, the integer table is all-reduced, rank 0 writes the report."""
-    from . import KMeans
+    rank folds its shard, the integer table is all-reduced, rank 0 writes the report.  With
+    ``--exemplars M`` the written report also carries every cluster's M nearest (``--farthest``:
+    farthest) rows and their distances (``KMeans.cluster_exemplars``, global row indices)."""
+    from . import KMeans, ops
     from .utils.io import load_points
 
+    if a.exemplars and not 1 <= a.exemplars <= ops.EXEMPLAR_MAX:
+        raise SystemExit(f"report: --exemplars must be in [1, {ops.EXEMPLAR_MAX}], got {a.exemplars}")
     comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     km = KMeans.load(a.model, device=comm.device)
     X, n, start = load_points(a.input, comm.rank, comm.world)
     rep = km.cluster_report(X.to(comm.device)).to_dict()
+    if a.exemplars:
+        from .api import _jsonable
+
+        rows, dist = km.cluster_exemplars(X.to(comm.device), a.exemplars, farthest=a.farthest)
+        rep["exemplars"] = _jsonable({"m": int(a.exemplars), "farthest": bool(a.farthest), "rows": rows.cpu(),
+                                      "distances": dist.cpu()})
     if comm.rank == 0:
         if a.output:
             Path(a.output).write_text(json.dumps(rep, indent=1))
@@ -413,6 +424,9 @@ def build_parser():
     rp.add_argument("--model", required=True)
     rp.add_argument("--input", required=True)
     rp.add_argument("--output", help="write the whole report here as JSON")
+    rp.add_argument("--exemplars", type=int, default=0, metavar="M",
+                    help="add every cluster's M rows nearest its centre (1..64) to the written report")
+    rp.add_argument("--farthest", action="store_true", help="with --exemplars: the M farthest rows instead")
     rp.add_argument("--device")
     b = sub.add_parser("blobs", help="write a synthetic dataset")
     b.add_argument("--n", type=int, required=True)

@@ -231,6 +231,33 @@ void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table
   hip_check(mk::launch_quality(a, stream(), (int)path), "quality_accumulate");
 }
 
+void exemplar_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t row0, bool farthest,
+                         int64_t path) {
+  TORCH_CHECK(idx.dim() == 2 && d2.dim() == 2 && idx.size(0) == d2.size(0) && idx.size(1) == d2.size(1) &&
+                  idx.size(1) >= 1,
+              "mikmeans: idx and d2 must both be [N, m_topk]");
+  const int64_t N = idx.size(0), mt = idx.size(1);
+  check_i32(idx, "idx", N * mt);
+  check_f32(d2, "d2", N * mt);
+  TORCH_CHECK(table.dim() == 2 && table.size(1) >= 1 && table.size(1) <= mk::EXEMPLAR_MAX,
+              "mikmeans: table must be [K, m] with 1 <= m <= ", mk::EXEMPLAR_MAX);
+  check_i64(table, "table", 1);
+  TORCH_CHECK(table.size(0) <= INT32_MAX && mt <= INT32_MAX, "mikmeans: too many clusters");
+  TORCH_CHECK(idx.get_device() == table.get_device() && d2.get_device() == table.get_device(),
+              "mikmeans: idx, d2 and table must share a device");
+  TORCH_CHECK(row0 >= 0 && row0 + N <= (int64_t(1) << 32),
+              "mikmeans: exemplar_accumulate takes row indices below 2^32 (row0 + N)");
+  mk::ExemplarArgs a;
+  a.idx = idx.data_ptr<int32_t>(); a.dist = d2.data_ptr<float>(); a.N = N; a.mt = (int)mt;
+  a.K = (int)table.size(0); a.m = (int)table.size(1);
+  a.row0 = (uint32_t)row0; a.farthest = farthest ? 1 : 0;
+  a.table = reinterpret_cast<unsigned long long*>(table.data_ptr<int64_t>());
+  TORCH_CHECK(path >= -1 && path <= 1 && (path < 1 || (int64_t)a.K * a.m <= mk::EXEMPLAR_LDS_MAX_WORDS),
+              "mikmeans: exemplar_accumulate path must be -1 (rule), 0 (global) or 1 (LDS, K * m <= ",
+              mk::EXEMPLAR_LDS_MAX_WORDS, ")");
+  hip_check(mk::launch_exemplars(a, stream(), (int)path), "exemplar_accumulate");
+}
+
 void update(const Tensor& X, const Tensor& labels, int64_t K, const Tensor& slab,
             const Tensor& cnt_slab, int64_t n_chunks, const c10::optional<Tensor>& weights,
             const Tensor& col_exp, int64_t cnt_exp, bool clamp,
@@ -860,7 +887,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("QUALITY_LDS_PASS_ROWS") = (int64_t)mk::QUALITY_LDS_BLOCKS * mk::QUALITY_LDS_THREADS;
   m.attr("QUALITY_LDS_MAX_K") = mk::QUALITY_LDS_MAX_K;
   m.attr("QUALITY_LDS_MIN_ROWS") = mk::QUALITY_LDS_MIN_ROWS;
-  m.def("reduce_cols", &reduce_cols, "lo sums of the wide-range columns (residual pass)");
+  m.def("exemplar_accumulate", &exemplar_accumulate,
+        "min-insert the top-1 output's rows into the per-cluster exemplar table [K, m] (64-bit integer atomic min)",
+        py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("row0") = 0, py::arg("farthest") = false,
+        py::arg("path") = -1);
+  m.def("exemplar_uses_lds", [](int64_t N, int64_t K, int64_t m) { return mk::exemplar_uses_lds(N, (int)K, (int)m); },
+        "whether a batch of N rows over K lists of m takes the LDS-private kernel");
+  m.attr("EXEMPLAR_MAX") = mk::EXEMPLAR_MAX;
+  m.attr("EXEMPLAR_LDS_MAX_WORDS") = mk::EXEMPLAR_LDS_MAX_WORDS;
+  m.attr("EXEMPLAR_LDS_MIN_ROWS") = mk::EXEMPLAR_LDS_MIN_ROWS;
+  m.attr("EXEMPLAR_LDS_RULE_KMM") = mk::EXEMPLAR_LDS_RULE_KMM;
+  m.def("reduce_cols", &reduce_cols,"lo sums of the wide-range columns (residual pass)");
   m.def("reduce", &reduce, "slab reduction into the packed f64 all-reduce message");
   m.def("label_delta", &label_delta, "changed-row list for the incremental M-step");
   m.def("label_delta_rows", &label_delta_rows, "changed-row list over a candidate list (bounded E-step)");

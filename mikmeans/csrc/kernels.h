@@ -144,6 +144,36 @@ struct QualityArgs {
 bool quality_uses_lds(int64_t N, int K);
 hipError_t launch_quality(const QualityArgs& a, hipStream_t s, int path = -1);
 
+// ---- per-cluster exemplar table (csrc/exemplars.hip) -------------------------------------
+// Min-inserts launch_topk's first column into table[K][m] (u64, all ones = empty, only ever
+// min-inserted into): slot j of cluster k is the (j+1)-th smallest key hi << 32 | row of its rows,
+// hi = bits(a^2) (nearest) or 0x7F7FFFFF - bits(a^2) (farthest), row = row0 + the row's index.
+constexpr int EXEMPLAR_MAX = 64;             // longest list
+constexpr int EXEMPLAR_THREADS = 256;
+constexpr int EXEMPLAR_MAX_BLOCKS = 2048;    // rows past EXEMPLAR_MAX_BLOCKS * EXEMPLAR_THREADS: the grid-stride loop
+// The LDS-private form: a [K][m] table in one workgroup's LDS (<= 160 KiB), one 1024-thread
+// workgroup per CU; it holds K * m <= EXEMPLAR_LDS_MAX_WORDS.  The launcher's rule takes it for
+// K * m^2 <= EXEMPLAR_LDS_RULE_KMM and N >= EXEMPLAR_LDS_MIN_ROWS: its flush costs every
+// workgroup K * m inserts of up to m steps on lists all workgroups share, so it pays for short
+// lists and few clusters and loses to the global form beyond (profiles/r7_02_exemplars.md).
+constexpr int EXEMPLAR_LDS_THREADS = 1024;
+constexpr int EXEMPLAR_LDS_BLOCKS = 256;
+constexpr int EXEMPLAR_LDS_MAX_WORDS = 160 * 1024 / 8;   // 20480
+constexpr int64_t EXEMPLAR_LDS_RULE_KMM = 16384;
+constexpr int64_t EXEMPLAR_LDS_MIN_ROWS = 8192;
+struct ExemplarArgs {
+  const int32_t* idx;          // [N, mt] centres, nearest first (column 0 is read)
+  const float* dist;           // [N, mt] their squared distances
+  int64_t N; int mt; int K;
+  int m;                       // list length, 1..EXEMPLAR_MAX
+  uint32_t row0;               // index of row 0 in the call's X; row0 + N <= 2^32
+  int farthest;
+  unsigned long long* table;   // [K, m]
+};
+// path: -1 the rule (exemplar_uses_lds), 0 the global-atomic kernel, 1 the LDS-private one.
+bool exemplar_uses_lds(int64_t N, int K, int m);
+hipError_t launch_exemplars(const ExemplarArgs& a, hipStream_t s, int path = -1);
+
 // ---- Hamerly bounds (csrc/rows.hip) ----------------------------------------------------
 // Moves every point's bounds by the last M-step's centre shifts (ub += |dc_label|,
 // lb -= the largest |dc_k| over k != label) and flags the points whose bounds no longer prove

@@ -31,6 +31,9 @@ __all__ = [
     "quality_accumulate",
     "quality_decode",
     "cluster_quality",
+    "exemplar_accumulate",
+    "exemplar_decode",
+    "cluster_exemplars",
 ]
 
 
@@ -360,6 +363,88 @@ def cluster_quality(X: torch.Tensor, centers: torch.Tensor, *, pack: "CentroidPa
     table = torch.zeros((centers.shape[0], QUALITY_WORDS), dtype=torch.int64, device=X.device)
     quality_rows(table, X, centers, pack=pack, block_rows=block_rows)
     return quality_decode(table, centers, X.dtype), table
+
+
+EXEMPLAR_MAX = cpu.EXEMPLAR_MAX     # csrc/kernels.h (the extension exports the same number)
+EXEMPLAR_BLOCK_ROWS = 1 << 22       # rows per top-1 pass of cluster_exemplars: 32 MB of (idx, d2) scratch
+
+
+def exemplar_new(K: int, m: int, device=None) -> torch.Tensor:
+    """An empty exemplar table: int64 ``[K, m]``, every word all ones."""
+    m = int(m)
+    if not 1 <= m <= EXEMPLAR_MAX:
+        raise ValueError(f"cluster_exemplars needs 1 <= m <= {EXEMPLAR_MAX}, got m = {m}")
+    return torch.full((int(K), m), cpu.EXEMPLAR_EMPTY, dtype=torch.int64, device=device)
+
+
+def exemplar_accumulate(table: torch.Tensor, idx: torch.Tensor, d2: torch.Tensor, *, row0: int = 0,
+                        farthest: bool = False, path: int = -1) -> torch.Tensor:
+    """Min-insert the rows of a top-m result (``idx`` int32, ``d2`` float32, ``[n, m_topk]`` as
+    :func:`topk` returns them; column 0 is read) into ``table`` (int64 ``[K, m]``, all ones
+    before the first call, :func:`exemplar_new`): slot j of cluster k ends as the (j+1)-th
+    smallest key ``hi << 32 | (row0 + row)`` of the cluster's rows, ``hi`` the bit pattern of the
+    squared distance (``farthest``: 0x7F7FFFFF minus it), so a list is the cluster's ``m``
+    nearest (farthest) rows, equal distances by the lower row (csrc/exemplars.hip has the
+    layout).  Rows with a label outside ``[0, K)`` or a non-finite distance are in no list.
+    64-bit integer atomic min only, so the table does not depend on the order or the blocking of
+    the rows.  GPU tensors run the native kernel (``path``: 0 forces its global-atomic form, 1
+    the LDS-private one, -1 the launcher's rule: tests and A/B runs), others the integer mirror
+    :func:`mikmeans.ops.cpu.exemplar_table` and :func:`mikmeans.ops.cpu.exemplar_merge`."""
+    if table.dim() != 2 or not 1 <= table.shape[1] <= EXEMPLAR_MAX or table.dtype != torch.int64:
+        raise ValueError(f"exemplar_accumulate needs an int64 [K, m] table with 1 <= m <= {EXEMPLAR_MAX}")
+    row0 = int(row0)
+    if row0 < 0 or row0 + idx.shape[0] > 1 << 32:
+        raise ValueError("exemplar_accumulate takes row indices below 2^32 (row0 + n): split the rows over calls")
+    if idx.is_cuda:
+        C = require()
+        assert C.EXEMPLAR_MAX == EXEMPLAR_MAX
+        C.exemplar_accumulate(idx.contiguous(), d2.contiguous(), table, row0, bool(farthest), path)
+        return table
+    part = cpu.exemplar_table(idx, d2, table.shape[0], table.shape[1], row0, farthest)
+    table.copy_(cpu.exemplar_merge(table, part))
+    return table
+
+
+def exemplar_decode(table: torch.Tensor, *, farthest: bool = False, row_start: int = 0):
+    """``(rows int64 [K, m], d2 float32 [K, m])`` of an exemplar table: each slot's row index
+    (plus ``row_start``) and squared distance, -1 and NaN for the empty slots."""
+    empty = table == cpu.EXEMPLAR_EMPTY
+    rows = torch.where(empty, -1, (table & 0xFFFFFFFF) + int(row_start))
+    hi = torch.where(empty, 0, table >> 32)
+    bits = (0x7F7FFFFF - hi) if farthest else hi
+    d2 = bits.to(torch.int32).view(torch.float32)
+    return rows, torch.where(empty, float("nan"), d2)
+
+
+def exemplar_rows(table: torch.Tensor, X: torch.Tensor, centers: torch.Tensor, *, row0: int = 0,
+                  farthest: bool = False, pack: "CentroidPack | None" = None,
+                  block_rows: int | None = None) -> torch.Tensor:
+    """Accumulate the rows of ``X`` (row i counted as ``row0 + i``) into ``table``: :func:`topk`
+    with m = 1 then :func:`exemplar_accumulate`, in row blocks (``block_rows``, default 2^22), so
+    the top-1 scratch stays bounded at any n.  The table does not depend on the block size."""
+    block = int(block_rows) if block_rows else EXEMPLAR_BLOCK_ROWS
+    if int(row0) < 0 or int(row0) + X.shape[0] > 1 << 32:
+        raise ValueError("cluster_exemplars takes fewer than 2^32 rows in one call")
+    if X.is_cuda and pack is None and X.shape[0] > block:   # pack the centres once for all blocks
+        X = pad_columns(X)
+        if dpad_for(X.shape[1], X.dtype):
+            pack = pack_centers(centers, X.shape[1], X.dtype, X.device)
+    for s in range(0, X.shape[0], block):
+        idx, d2 = topk(X[s : s + block], centers, 1, pack=pack)
+        exemplar_accumulate(table, idx, d2, row0=int(row0) + s, farthest=farthest)
+    return table
+
+
+def cluster_exemplars(X: torch.Tensor, centers: torch.Tensor, m: int, *, farthest: bool = False,
+                      pack: "CentroidPack | None" = None, block_rows: int | None = None):
+    """For every centre the ``m`` rows of ``X`` assigned to it that lie nearest it (``farthest``:
+    farthest from it): ``(rows int64 [K, m], d2 float32 [K, m], table)``, the squared distances
+    in list order, -1 / NaN where a cluster has fewer than ``m`` rows, and the int64 ``[K, m]``
+    table both were decoded from (on ``X``'s device)."""
+    table = exemplar_new(centers.shape[0], m, X.device)
+    exemplar_rows(table, X, centers, farthest=farthest, pack=pack, block_rows=block_rows)
+    rows, d2 = exemplar_decode(table, farthest=farthest)
+    return rows, d2, table
 
 
 def max_abs(X: torch.Tensor) -> float:

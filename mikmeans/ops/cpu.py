@@ -126,6 +126,69 @@ def quality_table(idx: torch.Tensor, d2: torch.Tensor, K: int) -> torch.Tensor:
     return table
 
 
+EXEMPLAR_MAX = 64           # csrc/kernels.h EXEMPLAR_MAX
+EXEMPLAR_EMPTY = -1         # the all-ones word: above every key in unsigned order
+_EX_FAR = 0x7F7FFFFF        # bits of the largest finite float
+_EX_LAST = (1 << 63) - 1    # stands in for the empty word while sorting (every key is below 2^63 - 2^32)
+
+
+def _exemplar_smallest(keys: torch.Tensor, m: int) -> torch.Tensor:
+    """Per row of int64 ``[K, w]`` keys, the ``m`` smallest distinct ones in unsigned order
+    (ascending, padded with the empty word)."""
+    K = keys.shape[0]
+    s = torch.where(keys == EXEMPLAR_EMPTY, _EX_LAST, keys).sort(dim=1).values
+    dup = torch.zeros_like(s, dtype=torch.bool)
+    dup[:, 1:] = s[:, 1:] == s[:, :-1]
+    s = torch.where(dup, _EX_LAST, s).sort(dim=1).values[:, :m]
+    if s.shape[1] < m:
+        s = torch.cat([s, torch.full((K, m - s.shape[1]), _EX_LAST, dtype=torch.int64, device=s.device)], 1)
+    return torch.where(s == _EX_LAST, EXEMPLAR_EMPTY, s)
+
+
+def exemplar_merge(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Per cluster, the m smallest keys of the union of two exemplar tables (int64 ``[K, m]``)
+    in unsigned order: what accumulating both tables' rows into one gives."""
+    if a.shape != b.shape or a.dim() != 2:
+        raise ValueError(f"exemplar_merge needs two [K, m] tables, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return _exemplar_smallest(torch.cat([a, b], 1), a.shape[1])
+
+
+def exemplar_table(idx: torch.Tensor, d2: torch.Tensor, K: int, m: int, row0: int = 0,
+                   farthest: bool = False) -> torch.Tensor:
+    """The per-cluster exemplar table int64 ``[K, m]`` of a top-m result (``idx`` int32, ``d2``
+    float32, both ``[n, m_topk]``, column 0 read): csrc/exemplars.hip in integer torch
+    arithmetic (its header has the key layout).  Slot j of cluster k holds the (j+1)-th smallest
+    key ``hi << 32 | (row0 + row)`` among the rows labelled k with a finite distance, -1 where
+    the cluster has fewer.  The CPU path and the test oracle."""
+    if idx.dim() != 2 or idx.shape != d2.shape or idx.shape[1] < 1:
+        raise ValueError(f"exemplar_table needs idx and d2 of one shape [n, m_topk], got {tuple(idx.shape)}, "
+                         f"{tuple(d2.shape)}")
+    m, row0 = int(m), int(row0)
+    if not 1 <= m <= EXEMPLAR_MAX:
+        raise ValueError(f"exemplar_table needs 1 <= m <= {EXEMPLAR_MAX}, got m = {m}")
+    if row0 < 0 or row0 + idx.shape[0] > 1 << 32:
+        raise ValueError("exemplar_table takes row indices below 2^32 (row0 + n)")
+    table = torch.full((K, m), EXEMPLAR_EMPTY, dtype=torch.int64, device=idx.device)
+    for s0 in range(0, idx.shape[0], 1 << 20):
+        k = idx[s0 : s0 + (1 << 20), 0].to(torch.int64)
+        d = d2[s0 : s0 + (1 << 20), 0].to(torch.float32)
+        row = torch.arange(s0, s0 + k.shape[0], dtype=torch.int64, device=idx.device) + row0
+        ok = (k >= 0) & (k < K) & torch.isfinite(d)
+        k, d, row = k[ok], d[ok], row[ok]
+        bits = (d.clamp_min(0.0) + 0.0).contiguous().view(torch.int32).to(torch.int64)   # (-0 -> +0)
+        key = ((_EX_FAR - bits if farthest else bits) << 32) | row
+        o = torch.argsort(key)                         # by key, then (stable) by cluster
+        o = o[torch.argsort(k[o], stable=True)]
+        k, key = k[o], key[o]
+        first = torch.cumsum(torch.bincount(k, minlength=K), 0) - torch.bincount(k, minlength=K)
+        rank = torch.arange(k.shape[0], dtype=torch.int64, device=idx.device) - first[k]
+        keep = rank < m
+        part = torch.full((K, m), EXEMPLAR_EMPTY, dtype=torch.int64, device=idx.device)
+        part[k[keep], rank[keep]] = key[keep]
+        table = part if s0 == 0 else exemplar_merge(table, part)
+    return table
+
+
 def cluster_sums(X: torch.Tensor, labels: torch.Tensor, K: int, weights=None):
     lab = labels.to(torch.int64)
     Xd = X.to(torch.float64)
