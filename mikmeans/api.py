@@ -454,6 +454,43 @@ class _Serving(_Params):
                                   X.shape[0], farthest, squared, fold)
         return (rows, d) if torch.is_tensor(X) else (rows.cpu().numpy(), d.cpu().numpy())
 
+    def cluster_quantiles(self, X, q=(0.5, 0.9, 0.99), *, squared: bool = False, block_rows: int | None = None):
+        """Exact per-cluster distance quantiles of ``X`` under the fitted centres: ``(values
+        [K, Q] float32, counts [K] int64)``.  ``values[k, j]`` is the distance below or at which a
+        share ``q[j]`` of the rows assigned to cluster ``k`` lie: the element at sorted position
+        ``clamp(ceil(q * n_k) - 1, 0, n_k - 1)`` of the cluster's distances (the "inverted CDF"
+        quantile: a real row's distance, never interpolated; ``q = 0`` the nearest row, ``q = 1``
+        the farthest), ``counts[k] = n_k`` the rows counted; a cluster without rows gives NaN.
+        ``q``: a number or up to 8 of them, each in [0, 1].  Distances are Euclidean as in
+        :meth:`transform` / :meth:`predict_topk` (``squared``: the kernel's squared values; cosine
+        models work on unit rows).
+
+        No sort: the top-1 kernel (:meth:`predict_topk`'s, on the serving pack) runs once and its
+        label and squared distance are kept (8 B per row on the device); csrc/quantiles.hip then
+        selects by radix over the distance bits, four passes of per-cluster 256-bin histograms
+        filled with integer atomics.  The result is bitwise the same from run to run and for any
+        ``block_rows`` (rows per top-1 pass; host rows bound for a GPU model are also copied in
+        blocks of that size).  In a multi-rank job ``X`` is the rank's shard, every pass's
+        histogram is all-reduced and every rank returns the one-rank result on the concatenated
+        shards.
+
+        A row's cluster and distance are :meth:`predict_topk`'s first column: the exact nearest
+        centre, the lower index on ties, as in :meth:`cluster_report`.  Rows whose distance is NaN
+        or infinite are not counted.  numpy in, numpy out."""
+        from . import ops
+
+        self._check_fitted()
+        c = self.cluster_centers_
+        qs = ops.quantile_levels(q)
+        chunks = []
+        self._fold_blocks(
+            X, lambda Xt, pk: chunks.extend(ops.quantile_top1(Xt, c, pack=pk, block_rows=block_rows)), block_rows)
+        comm = getattr(self, "comm", None) or get_comm()
+        reduce = comm.allreduce_ if comm is not None and comm.grouped else None
+        v, counts = ops.quantile_passes(chunks, c.shape[0], qs, c.device, reduce=reduce)
+        v = v if squared else v.sqrt()
+        return (v, counts) if torch.is_tensor(X) else (v.cpu().numpy(), counts.cpu().numpy())
+
     def transform(self, X):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine
         metric, between unit rows and unit centres: sqrt(2 - 2 cos)).  On the GPU: the MFMA
@@ -1299,6 +1336,23 @@ def cluster_exemplars(X, centers, m: int, dtype="float32", farthest: bool = Fals
     rows, d = _exemplar_lists(c.shape[0], m, dev, get_comm(), Xt.shape[0], farthest, False,
                               lambda table: ops.exemplar_rows(table, Xt, c, farthest=farthest))
     return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
+
+
+def cluster_quantiles(X, centers, q, dtype="float32"):
+    """Exact per-cluster quantiles of the Euclidean distances of the rows of ``X`` to the nearest
+    of the given ``centers``: ``(values [K, Q], counts [K])`` (``KMeans.cluster_quantiles`` without
+    a model; with a process group ``X`` is the rank's shard)."""
+    from . import ops
+
+    was_numpy = not torch.is_tensor(X)
+    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
+    dev = c.device if torch.is_tensor(centers) else _default_device(None)
+    Xt, _ = _to_tensor(X, dev, resolve_dtype(dtype))
+    comm = get_comm()
+    v, counts = ops.cluster_quantiles(Xt, c.to(dev), q,
+                                      reduce=comm.allreduce_ if comm is not None and comm.grouped else None)
+    v = v.sqrt()
+    return (v.cpu().numpy(), counts.cpu().numpy()) if was_numpy else (v, counts)
 
 
 def fit_predict(X, k: int, **kw):

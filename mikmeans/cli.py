@@ -139,12 +139,21 @@ def cmd_report(a) -> int:
     """Per-cluster quality of a dataset under a saved model (``KMeans.cluster_report``): every
     rank folds its shard, the integer table is all-reduced, rank 0 writes the report.  With
     ``--exemplars M`` the written report also carries every cluster's M nearest (``--farthest``:
-    farthest) rows and their distances (``KMeans.cluster_exemplars``, global row indices)."""
+    farthest) rows and their distances (``KMeans.cluster_exemplars``, global row indices), with
+    ``--quantiles 0.5,0.9,0.99`` every cluster's exact distance quantiles and the rows counted
+    (``KMeans.cluster_quantiles``)."""
     from . import KMeans, ops
     from .utils.io import load_points
 
     if a.exemplars and not 1 <= a.exemplars <= ops.EXEMPLAR_MAX:
         raise SystemExit(f"report: --exemplars must be in [1, {ops.EXEMPLAR_MAX}], got {a.exemplars}")
+    qs = None
+    if a.quantiles is not None:
+        try:
+            qs = ops.quantile_levels([float(v) for v in a.quantiles.split(",")])
+        except ValueError as e:
+            raise SystemExit(f"report: --quantiles takes 1 to {ops.QUANTILE_MAX_Q} comma-separated numbers in "
+                             f"[0, 1], got {a.quantiles!r} ({e})")
     comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     km = KMeans.load(a.model, device=comm.device)
     X, n, start = load_points(a.input, comm.rank, comm.world)
@@ -155,6 +164,11 @@ def cmd_report(a) -> int:
         rows, dist = km.cluster_exemplars(X.to(comm.device), a.exemplars, farthest=a.farthest)
         rep["exemplars"] = _jsonable({"m": int(a.exemplars), "farthest": bool(a.farthest), "rows": rows.cpu(),
                                       "distances": dist.cpu()})
+    if qs is not None:
+        from .api import _jsonable
+
+        dist, counts = km.cluster_quantiles(X.to(comm.device), qs)
+        rep["quantiles"] = _jsonable({"q": qs, "distances": dist.cpu(), "counts": counts.cpu()})
     if comm.rank == 0:
         if a.output:
             Path(a.output).write_text(json.dumps(rep, indent=1))
@@ -427,6 +441,9 @@ def build_parser():
     rp.add_argument("--exemplars", type=int, default=0, metavar="M",
                     help="add every cluster's M rows nearest its centre (1..64) to the written report")
     rp.add_argument("--farthest", action="store_true", help="with --exemplars: the M farthest rows instead")
+    rp.add_argument("--quantiles", metavar="Q,Q,...",
+                    help="add every cluster's exact distance quantiles (1..8 values in [0, 1], e.g. 0.5,0.9,0.99) "
+                         "to the written report")
     rp.add_argument("--device")
     b = sub.add_parser("blobs", help="write a synthetic dataset")
     b.add_argument("--n", type=int, required=True)

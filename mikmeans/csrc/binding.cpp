@@ -258,6 +258,79 @@ void exemplar_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& tabl
   hip_check(mk::launch_exemplars(a, stream(), (int)path), "exemplar_accumulate");
 }
 
+void quantile_hist(const Tensor& idx, const Tensor& d2, const Tensor& table, const c10::optional<Tensor>& prefix,
+                   int64_t pass, int64_t path, int64_t agg) {
+  TORCH_CHECK(idx.dim() == 2 && d2.dim() == 2 && idx.size(0) == d2.size(0) && idx.size(1) == d2.size(1) &&
+                  idx.size(1) >= 1,
+              "mikmeans: idx and d2 must both be [N, m_topk]");
+  const int64_t N = idx.size(0), mt = idx.size(1);
+  check_i32(idx, "idx", N * mt);
+  check_f32(d2, "d2", N * mt);
+  TORCH_CHECK(pass >= 0 && pass < mk::QUANTILE_PASSES, "mikmeans: quantile_hist pass must be 0..3, got ", pass);
+  TORCH_CHECK(table.dim() == (pass == 0 ? 2 : 3) && table.size(-1) == mk::QUANTILE_BINS,
+              "mikmeans: table must be [K, 256] in pass 0 and [K, Q, 256] in passes 1..3");
+  check_i64(table, "table", 1);
+  TORCH_CHECK(table.size(0) <= INT32_MAX && mt <= INT32_MAX, "mikmeans: too many clusters");
+  TORCH_CHECK(idx.get_device() == table.get_device() && d2.get_device() == table.get_device(),
+              "mikmeans: idx, d2 and table must share a device");
+  mk::QuantileHistArgs a;
+  a.idx = idx.data_ptr<int32_t>(); a.dist = d2.data_ptr<float>(); a.N = N; a.mt = (int)mt;
+  a.K = (int)table.size(0); a.Q = 1; a.pass = (int)pass; a.prefix = nullptr;
+  if (pass > 0) {
+    const int64_t Q = table.size(1);
+    TORCH_CHECK(Q >= 1 && Q <= mk::QUANTILE_MAX_Q, "mikmeans: quantile_hist needs 1 <= Q <= ", mk::QUANTILE_MAX_Q);
+    TORCH_CHECK(prefix.has_value() && prefix->dim() == 2 && prefix->size(0) == table.size(0) && prefix->size(1) == Q,
+                "mikmeans: prefix must be [K, Q]");
+    check_i32(*prefix, "prefix", table.size(0) * Q);
+    TORCH_CHECK(prefix->get_device() == table.get_device(), "mikmeans: prefix and table must share a device");
+    a.Q = (int)Q;
+    a.prefix = prefix->data_ptr<int32_t>();
+  }
+  const int64_t lists = mk::quantile_lists(a.K, a.Q, a.pass);
+  TORCH_CHECK(lists <= (int64_t(1) << 24), "mikmeans: quantile_hist takes at most 2^24 lists");
+  a.table = reinterpret_cast<unsigned long long*>(table.data_ptr<int64_t>());
+  TORCH_CHECK(agg >= -1 && agg <= mk::QUANTILE_AGG_MAX,
+              "mikmeans: quantile_hist agg must be -1 (the form's constant) or 0..", mk::QUANTILE_AGG_MAX);
+  a.agg = (int)agg;
+  const int64_t bands = mk::quantile_bands(lists);
+  TORCH_CHECK(path >= -1 && path <= 2 && (path < 1 || N < (int64_t(1) << 32)) && (path != 1 || bands <= 1) &&
+                  (path != 2 || bands <= mk::QUANTILE_BAND_LIMIT),
+              "mikmeans: quantile_hist path must be -1 (rule), 0 (global), 1 (LDS, lists <= ",
+              mk::QUANTILE_LDS_MAX_LISTS, ") or 2 (banded LDS, lists <= ",
+              mk::QUANTILE_LDS_MAX_LISTS * mk::QUANTILE_BAND_LIMIT, "), the LDS forms with fewer than 2^32 rows");
+  hip_check(mk::launch_quantile_hist(a, stream(), (int)path), "quantile_hist");
+}
+
+void quantile_select(const Tensor& table, const Tensor& q, const Tensor& prefix, const Tensor& rank,
+                     const Tensor& counts, int64_t pass) {
+  TORCH_CHECK(pass >= 0 && pass < mk::QUANTILE_PASSES, "mikmeans: quantile_select pass must be 0..3, got ", pass);
+  TORCH_CHECK(prefix.dim() == 2 && prefix.size(1) >= 1 && prefix.size(1) <= mk::QUANTILE_MAX_Q,
+              "mikmeans: prefix must be [K, Q] with 1 <= Q <= ", mk::QUANTILE_MAX_Q);
+  const int64_t K = prefix.size(0), Q = prefix.size(1);
+  TORCH_CHECK(K <= INT32_MAX, "mikmeans: too many clusters");
+  TORCH_CHECK(table.size(-1) == mk::QUANTILE_BINS && table.size(0) == K &&
+                  (pass == 0 ? table.dim() == 2 : table.dim() == 3 && table.size(1) == Q),
+              "mikmeans: table must be [K, 256] in pass 0 and [K, Q, 256] in passes 1..3");
+  check_i64(table, "table", 0);
+  check_i32(prefix, "prefix", K * Q);
+  check_i64(rank, "rank", K * Q);
+  check_i64(counts, "counts", K);
+  TORCH_CHECK(rank.dim() == 2 && rank.size(0) == K && rank.size(1) == Q && counts.dim() == 1 && counts.size(0) == K,
+              "mikmeans: rank must be [K, Q] and counts [K]");
+  check_cuda(q, "q");
+  TORCH_CHECK(q.scalar_type() == at::kDouble && q.is_contiguous() && q.dim() == 1 && q.size(0) == Q,
+              "mikmeans: q must be contiguous float64 [Q]");
+  const int dev = table.get_device();
+  TORCH_CHECK(q.get_device() == dev && prefix.get_device() == dev && rank.get_device() == dev &&
+                  counts.get_device() == dev,
+              "mikmeans: table, q, prefix, rank and counts must share a device");
+  mk::QuantileSelectArgs a;
+  a.table = reinterpret_cast<const unsigned long long*>(table.data_ptr<int64_t>());
+  a.q = q.data_ptr<double>(); a.prefix = prefix.data_ptr<int32_t>(); a.rank = rank.data_ptr<int64_t>();
+  a.counts = counts.data_ptr<int64_t>(); a.K = (int)K; a.Q = (int)Q; a.pass = (int)pass;
+  hip_check(mk::launch_quantile_select(a, stream()), "quantile_select");
+}
+
 void update(const Tensor& X, const Tensor& labels, int64_t K, const Tensor& slab,
             const Tensor& cnt_slab, int64_t n_chunks, const c10::optional<Tensor>& weights,
             const Tensor& col_exp, int64_t cnt_exp, bool clamp,
@@ -897,6 +970,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("EXEMPLAR_LDS_MAX_WORDS") = mk::EXEMPLAR_LDS_MAX_WORDS;
   m.attr("EXEMPLAR_LDS_MIN_ROWS") = mk::EXEMPLAR_LDS_MIN_ROWS;
   m.attr("EXEMPLAR_LDS_RULE_KMM") = mk::EXEMPLAR_LDS_RULE_KMM;
+  m.def("quantile_hist", &quantile_hist,
+        "add the top-1 output's rows into one radix-select pass's per-cluster digit histogram (64-bit integer atomic add)",
+        py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("prefix") = py::none(), py::arg("pass") = 0,
+        py::arg("path") = -1, py::arg("agg") = -1);
+  m.def("quantile_select", &quantile_select,
+        "per (cluster, q): the bin of the summed histogram that holds the remaining rank; updates prefix and rank",
+        py::arg("table"), py::arg("q"), py::arg("prefix"), py::arg("rank"), py::arg("counts"), py::arg("pass"));
+  m.def("quantile_uses_lds", [](int64_t N, int64_t lists) { return mk::quantile_uses_lds(N, lists); },
+        "whether a batch of N rows over `lists` histograms takes the LDS-private kernel");
+  m.def("quantile_path", [](int64_t N, int64_t lists, int64_t pass) { return mk::quantile_path(N, lists, (int)pass); },
+        "the launcher's rule for N rows over `lists` histograms in pass `pass`: 0 global, 1 LDS-private, 2 banded LDS",
+        py::arg("N"), py::arg("lists"), py::arg("pass") = 0);
+  m.attr("QUANTILE_BAND_LIMIT") = mk::QUANTILE_BAND_LIMIT;
+  m.attr("QUANTILE_BAND_MAX") = mk::QUANTILE_BAND_MAX;
+  m.attr("QUANTILE_BAND_MAX_PASS0") = mk::QUANTILE_BAND_MAX_PASS0;
+  m.attr("QUANTILE_BAND_MIN_ROWS") = mk::QUANTILE_BAND_MIN_ROWS;
+  m.attr("QUANTILE_MAX_Q") = mk::QUANTILE_MAX_Q;
+  m.attr("QUANTILE_BINS") = mk::QUANTILE_BINS;
+  m.attr("QUANTILE_LDS_MAX_LISTS") = mk::QUANTILE_LDS_MAX_LISTS;
+  m.attr("QUANTILE_LDS_MIN_ROWS") = mk::QUANTILE_LDS_MIN_ROWS;
+  m.attr("QUANTILE_AGG_ROUNDS") = mk::QUANTILE_AGG_ROUNDS;
+  m.attr("QUANTILE_LDS_AGG_ROUNDS") = mk::QUANTILE_LDS_AGG_ROUNDS;
   m.def("reduce_cols", &reduce_cols,"lo sums of the wide-range columns (residual pass)");
   m.def("reduce", &reduce, "slab reduction into the packed f64 all-reduce message");
   m.def("label_delta", &label_delta, "changed-row list for the incremental M-step");

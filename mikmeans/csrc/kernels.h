@@ -174,6 +174,79 @@ struct ExemplarArgs {
 bool exemplar_uses_lds(int64_t N, int K, int m);
 hipError_t launch_exemplars(const ExemplarArgs& a, hipStream_t s, int path = -1);
 
+// ---- per-cluster distance quantiles (csrc/quantiles.hip) ----------------------------------
+// Exact order statistics of every cluster's a^2 = max(dist[i, 0], +0) by a most-significant-
+// digit radix select over the distance bits: four passes of 8-bit digits (shift 24, 16, 8, 0),
+// each a histogram of launch_topk's first column (u64, only ever added into) and a select that
+// fixes one more byte of every (cluster, q) pair's prefix and updates its remaining rank.
+constexpr int QUANTILE_MAX_Q = 8;            // most quantiles in one call
+constexpr int QUANTILE_BINS = 256;           // one digit
+constexpr int QUANTILE_PASSES = 4;
+constexpr int QUANTILE_THREADS = 256;
+constexpr int QUANTILE_MAX_BLOCKS = 2048;    // rows past QUANTILE_MAX_BLOCKS * QUANTILE_THREADS: the grid-stride loop
+// The LDS-private form: a [lists][256] u32 table in one workgroup's LDS (<= 160 KiB), one
+// 1024-thread workgroup per CU; lists = K (pass 0) or K * Q (passes 1..3).  A launch takes fewer
+// than 2^32 rows, so a u32 bin cannot wrap.  The launcher's rule takes it wherever the lists fit
+// and N >= QUANTILE_LDS_MIN_ROWS: measured (profiles/r7_03_quantiles.md) it is 3 to 200 times
+// faster in passes 0 and 1, 0.01 to 0.04 ms slower in passes 2 and 3 on distances without
+// ties (where it stays because equal distances put every row of a cluster on one global word),
+// and from 8192 rows on never more than 4 us behind.
+constexpr int QUANTILE_LDS_THREADS = 1024;
+constexpr int QUANTILE_LDS_BLOCKS = 256;
+constexpr int QUANTILE_LDS_MAX_LISTS = 160 * 1024 / (QUANTILE_BINS * 4);   // 160
+constexpr int64_t QUANTILE_LDS_MIN_ROWS = 8192;
+// The banded form: the same kernel for more lists than one workgroup's LDS holds.  Band b (the
+// grid's y) keeps lists [160 b, 160 b + 160) in LDS, reads every row and skips the rows of other
+// bands: ceil(lists / 160) sweeps over the 8 B rows instead of a global atomic per row.  It
+// holds up to QUANTILE_BAND_LIMIT bands.  Measured (profiles/r7_03_quantiles.md, N = 10^7): a
+// sweep costs 0.013 ms in pass 0, where the global form's rows meet on one to three words per
+// cluster (7 bands 0.10, 26 bands 0.33 against 0.44 ms), and 0.03 to 0.08 ms in pass 1 (3 bands
+// 0.19 against 1.0, 8 bands 0.64 against 1.8, 26 bands 0.57 against 0.26 ms); in passes 2 and 3
+// few rows match a prefix and the global form (0.03 to 0.3 ms) always wins.  The launcher's
+// rule takes it in pass 0 up to QUANTILE_BAND_MAX_PASS0 bands and in pass 1 up to
+// QUANTILE_BAND_MAX, from QUANTILE_BAND_MIN_ROWS rows on.
+constexpr int QUANTILE_BAND_LIMIT = 64;
+constexpr int QUANTILE_BAND_MAX_PASS0 = 26;
+constexpr int QUANTILE_BAND_MAX = 8;
+constexpr int64_t QUANTILE_BAND_MIN_ROWS = 1 << 18;
+// Wave aggregation: up to this many rounds of "the first pending lane's (list, digit) key, a
+// ballot of the lanes that share it, one add of their count"; lanes still pending afterwards add
+// one each; 0 switches it off.  The global form takes QUANTILE_AGG_ROUNDS, the LDS-private form
+// QUANTILE_LDS_AGG_ROUNDS (A/B runs pass their own count).  Measured
+// (profiles/r7_03_quantiles.md): on the global form two rounds cost rows in random order under
+// 1 % and take pass 0 on rows ordered by label from 0.74 to 0.045 ms (K = 1024), more rounds
+// only add to the later passes; LDS atomics on one address need no help, every round there is
+// a loss.
+constexpr int QUANTILE_AGG_ROUNDS = 2;
+constexpr int QUANTILE_LDS_AGG_ROUNDS = 0;
+constexpr int QUANTILE_AGG_MAX = 64;
+struct QuantileHistArgs {
+  const int32_t* idx;          // [N, mt] centres, nearest first (column 0 is read)
+  const float* dist;           // [N, mt] their squared distances
+  int64_t N; int mt; int K;
+  int Q;                       // quantiles, 1..QUANTILE_MAX_Q (pass 0 does not read it)
+  int pass;                    // 0..3: the digit at shift 24 - 8 * pass
+  const int32_t* prefix;       // [K, Q] the bits fixed so far (passes 1..3)
+  unsigned long long* table;   // pass 0: [K, 256]; passes 1..3: [K, Q, 256]
+  int agg;                     // wave-aggregation rounds, 0..QUANTILE_AGG_MAX; -1: the form's constant
+};
+struct QuantileSelectArgs {
+  const unsigned long long* table;   // as above, summed over all rows (and ranks)
+  const double* q;                   // [Q], each in [0, 1]
+  int32_t* prefix;                   // [K, Q] in / out
+  int64_t* rank;                     // [K, Q] in (passes 1..3) / out: the rank left below the prefix
+  int64_t* counts;                   // [K] out (pass 0): n_k
+  int K; int Q; int pass;
+};
+// path: -1 the rule (quantile_path), 0 the global-atomic kernel, 1 the LDS-private one (the lists
+// fit one workgroup), 2 the banded LDS one.
+__host__ __device__ inline int64_t quantile_lists(int K, int Q, int pass) { return pass == 0 ? (int64_t)K : (int64_t)K * Q; }
+inline int64_t quantile_bands(int64_t lists) { return (lists + QUANTILE_LDS_MAX_LISTS - 1) / QUANTILE_LDS_MAX_LISTS; }
+bool quantile_uses_lds(int64_t N, int64_t lists);
+int quantile_path(int64_t N, int64_t lists, int pass);
+hipError_t launch_quantile_hist(const QuantileHistArgs& a, hipStream_t s, int path = -1);
+hipError_t launch_quantile_select(const QuantileSelectArgs& a, hipStream_t s);
+
 // ---- Hamerly bounds (csrc/rows.hip) ----------------------------------------------------
 // Moves every point's bounds by the last M-step's centre shifts (ub += |dc_label|,
 // lb -= the largest |dc_k| over k != label) and flags the points whose bounds no longer prove

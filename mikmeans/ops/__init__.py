@@ -34,6 +34,10 @@ __all__ = [
     "exemplar_accumulate",
     "exemplar_decode",
     "cluster_exemplars",
+    "quantile_state",
+    "quantile_hist",
+    "quantile_select",
+    "cluster_quantiles",
 ]
 
 
@@ -445,6 +449,131 @@ def cluster_exemplars(X: torch.Tensor, centers: torch.Tensor, m: int, *, farthes
     exemplar_rows(table, X, centers, farthest=farthest, pack=pack, block_rows=block_rows)
     rows, d2 = exemplar_decode(table, farthest=farthest)
     return rows, d2, table
+
+
+QUANTILE_MAX_Q = cpu.QUANTILE_MAX_Q     # csrc/kernels.h (the extension exports the same number)
+QUANTILE_BINS = cpu.QUANTILE_BINS
+QUANTILE_PASSES = cpu.QUANTILE_PASSES
+QUANTILE_BLOCK_ROWS = 1 << 22           # rows per top-1 pass of cluster_quantiles
+
+
+def quantile_levels(q) -> list[float]:
+    """``q`` (a number or a sequence of them) as a list of 1..QUANTILE_MAX_Q floats in [0, 1]."""
+    try:
+        qs = torch.as_tensor(q, dtype=torch.float64).reshape(-1).tolist()
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise ValueError(f"cluster_quantiles needs numbers in [0, 1], got {q!r}") from e
+    if not 1 <= len(qs) <= QUANTILE_MAX_Q:
+        raise ValueError(f"cluster_quantiles takes 1 to {QUANTILE_MAX_Q} quantiles in one call, got {len(qs)}")
+    for v in qs:
+        if not 0.0 <= v <= 1.0:                      # (NaN fails both comparisons)
+            raise ValueError(f"cluster_quantiles needs every q finite and in [0, 1], got {v}")
+    return qs
+
+
+def quantile_state(K: int, Q: int, device=None):
+    """The radix select's state before pass 0: ``(prefix int32 [K, Q], rank int64 [K, Q], counts
+    int64 [K])``, all zero."""
+    K, Q = int(K), int(Q)
+    if not 1 <= Q <= QUANTILE_MAX_Q:
+        raise ValueError(f"cluster_quantiles takes 1 to {QUANTILE_MAX_Q} quantiles in one call, got {Q}")
+    return (torch.zeros((K, Q), dtype=torch.int32, device=device), torch.zeros((K, Q), dtype=torch.int64, device=device),
+            torch.zeros(K, dtype=torch.int64, device=device))
+
+
+def quantile_hist(idx: torch.Tensor, d2: torch.Tensor, K: int, prefix: torch.Tensor, pass_: int, *,
+                  table: torch.Tensor | None = None, path: int = -1, agg: int = -1) -> torch.Tensor:
+    """Add the rows of a top-m result (``idx`` int32, ``d2`` float32, ``[n, m_topk]`` as
+    :func:`topk` returns them; column 0 is read) into pass ``pass_``'s digit histogram ``table``
+    (int64 ``[K, 256]`` in pass 0, ``[K, Q, 256]`` in passes 1..3; a zero one is made when none is
+    given) and return it: in pass 0 a row adds one to ``(k, bits >> 24)``, later to
+    ``(k, j, (bits >> s) & 255)`` for every j whose ``prefix`` (int32 ``[K, Q]``) shares its bits
+    above ``s + 8`` (csrc/quantiles.hip has the passes).  Rows with a label outside ``[0, K)`` or a
+    non-finite distance count nowhere.  64-bit integer atomic add only, so the table does not
+    depend on the order or the blocking of the rows.  GPU tensors run the native kernel
+    (``path``: 0 forces its global-atomic form, 1 the LDS-private one, 2 the banded LDS one, -1
+    the launcher's rule; ``agg``: the wave-aggregation rounds, -1 the form's constant: tests and
+    A/B runs), others
+    the integer mirror :func:`mikmeans.ops.cpu.quantile_hist`."""
+    K, pass_ = int(K), int(pass_)
+    if not 0 <= pass_ < QUANTILE_PASSES:
+        raise ValueError(f"quantile_hist needs a pass in 0..3, got {pass_}")
+    Q = int(prefix.shape[1])
+    shape = (K, QUANTILE_BINS) if pass_ == 0 else (K, Q, QUANTILE_BINS)
+    if table is None:
+        table = torch.zeros(shape, dtype=torch.int64, device=idx.device)
+    if tuple(table.shape) != shape or table.dtype != torch.int64:
+        raise ValueError(f"quantile_hist needs an int64 {list(shape)} table in pass {pass_}")
+    if idx.is_cuda:
+        C = require()
+        assert C.QUANTILE_MAX_Q == QUANTILE_MAX_Q and C.QUANTILE_BINS == QUANTILE_BINS
+        C.quantile_hist(idx.contiguous(), d2.contiguous(), table, prefix if pass_ else None, pass_, path, agg)
+        return table
+    table += cpu.quantile_hist(idx, d2, K, prefix, pass_)
+    return table
+
+
+def quantile_select(table: torch.Tensor, q: torch.Tensor, prefix: torch.Tensor, rank: torch.Tensor,
+                    counts: torch.Tensor, pass_: int) -> None:
+    """One select step on pass ``pass_``'s summed histogram, in place: per (cluster, q) the
+    smallest bin whose running count exceeds the remaining rank joins ``prefix`` at shift
+    ``24 - 8 * pass_`` and ``rank`` drops by the count below it; pass 0 first writes ``counts`` =
+    n_k and derives the rank r = clamp(ceil(q * n_k) - 1, 0, n_k - 1) from ``q`` (float64
+    ``[Q]``).  GPU tensors run the native kernel, others :func:`mikmeans.ops.cpu.quantile_select`."""
+    if table.is_cuda:
+        require().quantile_select(table, q, prefix, rank, counts, int(pass_))
+        return
+    P, R, n = cpu.quantile_select(table, q, prefix, rank, pass_)
+    prefix.copy_(P)
+    rank.copy_(R)
+    if n is not None:
+        counts.copy_(n)
+
+
+def quantile_top1(X: torch.Tensor, centers: torch.Tensor, *, pack: "CentroidPack | None" = None,
+                  block_rows: int | None = None) -> list:
+    """The top-1 ``(idx, d2)`` of every row of ``X``, a list of one pair per row block
+    (``block_rows``, default 2^22): the 8 B per row that the four histogram passes of
+    :func:`quantile_passes` read."""
+    block = int(block_rows) if block_rows else QUANTILE_BLOCK_ROWS
+    if X.is_cuda and pack is None and X.shape[0] > block:   # pack the centres once for all blocks
+        X = pad_columns(X)
+        if dpad_for(X.shape[1], X.dtype):
+            pack = pack_centers(centers, X.shape[1], X.dtype, X.device)
+    return [topk(X[s : s + block], centers, 1, pack=pack) for s in range(0, X.shape[0], block)]
+
+
+def quantile_passes(chunks, K: int, q, device=None, *, reduce=None):
+    """The radix select over kept top-1 output (``chunks``: ``(idx, d2)`` pairs, fewer than 2^32
+    rows each): ``(d2_values float32 [K, Q], counts int64 [K])``, per cluster and ``q`` the
+    squared distance at sorted position clamp(ceil(q * n_k) - 1, 0, n_k - 1) of the cluster's
+    rows, NaN for a cluster without rows.  ``reduce`` (a callable, in place) is applied to each
+    pass's histogram before its select: a multi-rank job's all-reduce.  No host read between
+    the passes."""
+    qs = quantile_levels(q)
+    qt = torch.tensor(qs, dtype=torch.float64, device=device)
+    prefix, rank, counts = quantile_state(K, len(qs), device)
+    for p in range(QUANTILE_PASSES):
+        shape = (int(K), QUANTILE_BINS) if p == 0 else (int(K), len(qs), QUANTILE_BINS)
+        table = torch.zeros(shape, dtype=torch.int64, device=device)
+        for idx, d2 in chunks:
+            quantile_hist(idx, d2, K, prefix, p, table=table)
+        if reduce is not None:
+            reduce(table)
+        quantile_select(table, qt, prefix, rank, counts, p)
+    values = torch.where((counts > 0)[:, None], prefix.view(torch.float32), float("nan"))
+    return values, counts
+
+
+def cluster_quantiles(X: torch.Tensor, centers: torch.Tensor, q, *, pack: "CentroidPack | None" = None,
+                      block_rows: int | None = None, reduce=None):
+    """Exact per-cluster quantiles of the squared distances of the rows of ``X`` to their nearest
+    centre: ``(d2_values float32 [K, Q], counts int64 [K])``.  One top-1 pass in row blocks, its
+    ``(idx, d2)`` kept (8 B per row), then four histogram passes over it (:func:`quantile_passes`);
+    no sort, and every value is a real row's squared distance bit for bit."""
+    quantile_levels(q)
+    chunks = quantile_top1(X, centers, pack=pack, block_rows=block_rows)
+    return quantile_passes(chunks, centers.shape[0], q, X.device, reduce=reduce)
 
 
 def max_abs(X: torch.Tensor) -> float:

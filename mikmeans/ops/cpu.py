@@ -189,6 +189,79 @@ def exemplar_table(idx: torch.Tensor, d2: torch.Tensor, K: int, m: int, row0: in
     return table
 
 
+QUANTILE_MAX_Q = 8          # csrc/kernels.h QUANTILE_MAX_Q
+QUANTILE_BINS = 256         # one 8-bit digit
+QUANTILE_PASSES = 4         # shift 24, 16, 8, 0
+
+
+def quantile_hist(idx: torch.Tensor, d2: torch.Tensor, K: int, prefix: torch.Tensor | None, pass_: int) -> torch.Tensor:
+    """One radix-select pass's digit histogram of a top-m result (``idx`` int32, ``d2`` float32,
+    both ``[n, m_topk]``, column 0 read): csrc/quantiles.hip in integer torch arithmetic (its
+    header has the passes).  Pass 0: int64 ``[K, 256]``, a row labelled k with a finite distance
+    adds one to ``(k, bits >> 24)``, ``bits`` the bit pattern of max(d2, +0).  Passes 1..3
+    (``prefix`` int32 ``[K, Q]``): int64 ``[K, Q, 256]``, the row adds one to
+    ``(k, j, (bits >> s) & 255)`` for every j whose prefix shares its bits above ``s + 8``,
+    ``s = 24 - 8 * pass``.  The CPU path and the test oracle."""
+    if idx.dim() != 2 or idx.shape != d2.shape or idx.shape[1] < 1:
+        raise ValueError(f"quantile_hist needs idx and d2 of one shape [n, m_topk], got {tuple(idx.shape)}, "
+                         f"{tuple(d2.shape)}")
+    pass_, K = int(pass_), int(K)
+    if not 0 <= pass_ < QUANTILE_PASSES:
+        raise ValueError(f"quantile_hist needs a pass in 0..3, got {pass_}")
+    if pass_ and (prefix is None or prefix.dim() != 2 or prefix.shape[0] != K
+                  or not 1 <= prefix.shape[1] <= QUANTILE_MAX_Q):
+        raise ValueError(f"quantile_hist needs a [K, Q] prefix with 1 <= Q <= {QUANTILE_MAX_Q} in passes 1..3")
+    Q = prefix.shape[1] if pass_ else 1
+    s = 24 - 8 * pass_
+    flat = torch.zeros(K * Q * QUANTILE_BINS, dtype=torch.int64, device=idx.device)
+    for s0 in range(0, idx.shape[0], 1 << 20):
+        k = idx[s0 : s0 + (1 << 20), 0].to(torch.int64)
+        d = d2[s0 : s0 + (1 << 20), 0].to(torch.float32)
+        ok = (k >= 0) & (k < K) & torch.isfinite(d)
+        k, d = k[ok], d[ok]
+        bits = (d.clamp_min(0.0) + 0.0).contiguous().view(torch.int32).to(torch.int64)   # (-0 -> +0)
+        digit = (bits >> s) & 255
+        if pass_ == 0:
+            flat += torch.bincount(k * QUANTILE_BINS + digit, minlength=flat.shape[0])
+            continue
+        for j in range(Q):
+            hit = (bits >> (s + 8)) == (prefix[k, j].to(torch.int64) >> (s + 8))
+            flat += torch.bincount(((k * Q + j) * QUANTILE_BINS + digit)[hit], minlength=flat.shape[0])
+    return flat.view(K, QUANTILE_BINS) if pass_ == 0 else flat.view(K, Q, QUANTILE_BINS)
+
+
+def quantile_select(table: torch.Tensor, q: torch.Tensor, prefix: torch.Tensor, rank: torch.Tensor, pass_: int):
+    """One select step on a summed histogram: ``(prefix int32 [K, Q], rank int64 [K, Q], counts
+    int64 [K] or None)``.  Pass 0 (``table`` ``[K, 256]``; ``prefix`` and ``rank`` give the shape
+    only): ``counts`` = n_k, r = clamp(ceil(q * n_k) - 1, 0, n_k - 1) with the product one float64
+    multiply, b the smallest bin whose running count exceeds r, prefix = b << 24 and rank = r - the
+    count below b.  Passes 1..3 (``[K, Q, 256]``): the same from the given rank, prefix |= b << s.
+    A pair whose bins hold no more than its rank (an empty cluster) keeps prefix and rank (zeros
+    from pass 0)."""
+    pass_ = int(pass_)
+    K, Q = prefix.shape
+    s = 24 - 8 * pass_
+    counts = None
+    if pass_ == 0:
+        counts = table.sum(1)
+        r = torch.ceil(q.to(torch.float64)[None, :] * counts.to(torch.float64)[:, None]).to(torch.int64) - 1
+        R = torch.minimum(r, counts[:, None] - 1).clamp_min(0)
+        H = table[:, None, :].expand(K, Q, QUANTILE_BINS)
+        P = torch.zeros((K, Q), dtype=torch.int64, device=table.device)
+        keepR = torch.zeros_like(R)
+    else:
+        R, H, P = rank.to(torch.int64), table, prefix.to(torch.int64)
+        keepR = R
+    cum = H.cumsum(-1)
+    over = cum > R[..., None]
+    has = over.any(-1)
+    b = over.to(torch.int8).argmax(-1)                      # the first bin past the rank
+    below = (cum - H).gather(-1, b[..., None])[..., 0]
+    P = torch.where(has, P | (b << s), P)
+    R = torch.where(has, R - below, keepR)
+    return P.to(torch.int32), R, counts
+
+
 def cluster_sums(X: torch.Tensor, labels: torch.Tensor, K: int, weights=None):
     lab = labels.to(torch.int64)
     Xd = X.to(torch.float64)
