@@ -27,6 +27,7 @@ from .config import KMeansConfig, resolve_dtype
 from .models.init import resolve_init
 from .models.lloyd import LloydEngine, tol_to_abs
 from .models.minibatch import MiniBatchEngine
+from . import ops
 from .ops import pad_columns
 from .parallel.comm import Comm, get_comm
 from .utils import faults
@@ -114,6 +115,11 @@ def _shard_info(n_local: int, comm: Comm, device):
     return int(sizes.sum()), start
 
 
+def _allreduce(comm):
+    """The in-place sum over the ranks of ``comm``, or None where there is nothing to sum over."""
+    return comm.allreduce_ if comm is not None and comm.grouped else None
+
+
 def _jsonable(v):
     """Plain JSON values: lists for arrays, None for NaN, "Infinity" for an infinite float."""
     if isinstance(v, dict):
@@ -161,8 +167,6 @@ class ClusterReport:
 
     @classmethod
     def from_table(cls, table: torch.Tensor, centers: torch.Tensor, dtype):
-        from . import ops
-
         rep = ops.quality_decode(table, centers, dtype)
         for k in cls.PER_CLUSTER:
             rep[k] = rep[k].to(table.device)
@@ -185,13 +189,12 @@ class ClusterReport:
 def _report_table(centers, comm, dtype, fold) -> ClusterReport:
     """``fold(table)`` accumulates this rank's rows; the table is then summed (its maximum
     word maximised) over the ranks of ``comm`` and decoded, the same on every rank."""
-    from . import ops
-
     table = torch.zeros((centers.shape[0], ops.QUALITY_WORDS), dtype=torch.int64, device=centers.device)
     fold(table)
-    if comm is not None and comm.grouped:
+    reduce = _allreduce(comm)
+    if reduce is not None:
         mx = table[:, 17].clone()
-        comm.allreduce_(table)
+        reduce(table)
         comm.allreduce_max_(mx)
         table[:, 17] = mx
     return ClusterReport.from_table(table, centers, dtype)
@@ -203,13 +206,11 @@ def _exemplar_lists(K: int, m: int, device, comm, n_local: int, farthest: bool, 
     (key word, global row) pairs all-gathered, the m lexicographically smallest kept per
     cluster -- and decoded: ``(rows int64 [K, m], distances float32 [K, m])``, the same on every
     rank and bit for bit the one-rank result on the concatenated shards."""
-    from . import ops
-
     if int(n_local) >= 1 << 32:
         raise ValueError(f"cluster_exemplars takes fewer than 2^32 rows in one call, got {int(n_local)}")
     table = ops.exemplar_new(K, m, device)
     fold(table)
-    if comm is not None and comm.grouped:
+    if _allreduce(comm) is not None:
         _, start = _shard_info(int(n_local), comm, device)
         rows, _ = ops.exemplar_decode(table, row_start=start)
         last = 1 << 62                                        # (past every key word: they are below 2^31)
@@ -287,8 +288,6 @@ class _Serving(_Params):
     def _serving_pack(self, Xt):
         """The fitted centres packed for the assign kernel, built once and reused by every
         predict/score call until the centres change (serving: one kernel launch per batch)."""
-        from . import ops
-
         c = self.cluster_centers_
         if not Xt.is_cuda or not c.is_cuda:
             return None
@@ -318,37 +317,43 @@ class _Serving(_Params):
                 Xt = _unit_rows(Xt)
         return Xt, was_numpy
 
-    def _row_blocks(self, X, run, block_rows: int | None = None):
-        """``run(Xt, pack)`` -- a tuple of per-row tensors (or None) -- over every row of X:
-        ``(outputs, was_numpy)``.  Host rows bound for a GPU model go through in blocks of
-        ~256 MB (or ``block_rows``: a host-shard fit labels its rows in batch-sized blocks,
-        the memory plan's), so a shard larger than HBM (a streamed fit's) is never copied to
-        the device whole."""
+    def _host_blocks(self, X, block_rows: int | None = None):
+        """``(start, Xt, pack)`` over the rows of X, ``Xt`` ready for the kernels
+        (:meth:`_inputs`) and ``pack`` the serving pack.  Device rows and CPU models go through
+        in one piece.  Host rows bound for a GPU model go through in blocks of ~256 MB (or
+        ``block_rows``: a host-shard fit labels its rows in batch-sized blocks, the memory
+        plan's), so a shard larger than HBM (a streamed fit's) is never copied to the device
+        whole.  An empty X still gives one (empty) block."""
         dev = self.cluster_centers_.device
-        host = not (torch.is_tensor(X) and X.device == dev)
         n = X.shape[0]
-        if dev.type != "cuda" or not host or n == 0:
-            Xt, was_numpy = self._inputs(X)
-            return tuple(run(Xt, self._serving_pack(Xt))), was_numpy
-        was_numpy = not torch.is_tensor(X)
-        block = int(block_rows) if block_rows else max(1, (1 << 28) // max(1, X.shape[1] * 4))
+        block = n
+        if dev.type == "cuda" and not (torch.is_tensor(X) and X.device == dev):
+            block = int(block_rows) if block_rows else max(1, (1 << 28) // max(1, X.shape[1] * 4))
+        for i in range(0, max(n, 1), max(block, 1)):
+            Xt, _ = self._inputs(X[i : i + block] if block < n else X)
+            yield i, Xt, self._serving_pack(Xt)
+
+    def _row_blocks(self, X, run, block_rows: int | None = None):
+        """``run(Xt, pack)`` -- a tuple of per-row tensors (or None) -- over every row of X
+        (:meth:`_host_blocks`): ``(outputs, was_numpy)``."""
+        n = X.shape[0]
         outs = None
-        for i in range(0, n, block):
-            Xt, _ = self._inputs(X[i : i + block])
-            part = run(Xt, self._serving_pack(Xt))
+        for i, Xt, pk in self._host_blocks(X, block_rows):
+            part = run(Xt, pk)
+            if Xt.shape[0] == n:
+                outs = part
+                break
             if outs is None:
-                outs = [None if p is None else torch.empty((n, *p.shape[1:]), dtype=p.dtype, device=dev)
+                outs = [None if p is None else torch.empty((n, *p.shape[1:]), dtype=p.dtype, device=p.device)
                         for p in part]
             for o, p in zip(outs, part):
                 if o is not None:
-                    o[i : i + block] = p
-        return tuple(outs), was_numpy
+                    o[i : i + Xt.shape[0]] = p
+        return tuple(outs), not torch.is_tensor(X)
 
     def _assign_rows(self, X, with_dist: bool, block_rows: int | None = None):
         """(labels, squared distances or None) of every row of X under the fitted centres
         (host rows in blocks, :meth:`_row_blocks`)."""
-        from . import ops
-
         (lab, mind), was_numpy = self._row_blocks(
             X, lambda Xt, pk: ops.assign(Xt, self.cluster_centers_, with_dist=with_dist, pack=pk), block_rows)
         return lab, mind, was_numpy
@@ -361,8 +366,6 @@ class _Serving(_Params):
         fused top-m kernel on the serving pack (csrc/topk.hip) -- the ``[n, K]`` distance
         matrix is never written.  numpy in, numpy out; host rows bound for a GPU model go
         through in blocks (``block_rows``) as in :meth:`predict`."""
-        from . import ops
-
         self._check_fitted()
         m = int(m)
         K = int(self.cluster_centers_.shape[0])
@@ -372,18 +375,6 @@ class _Serving(_Params):
             X, lambda Xt, pk: ops.topk(Xt, self.cluster_centers_, m, pack=pk), block_rows)
         d = d2 if squared else d2.sqrt()
         return (idx.cpu().numpy(), d.cpu().numpy()) if was_numpy else (idx, d)
-
-    def _fold_blocks(self, X, run, block_rows: int | None = None) -> None:
-        """``run(Xt, pack)`` over every row of X for its side effect (an accumulation), host
-        rows bound for a GPU model in blocks as :meth:`_row_blocks` takes them."""
-        dev = self.cluster_centers_.device
-        host = not (torch.is_tensor(X) and X.device == dev)
-        n = X.shape[0]
-        block = n if dev.type != "cuda" or not host or n == 0 else (
-            int(block_rows) if block_rows else max(1, (1 << 28) // max(1, X.shape[1] * 4)))
-        for i in range(0, max(n, 1), max(block, 1)):
-            Xt, _ = self._inputs(X[i : i + block] if block < n else X)
-            run(Xt, self._serving_pack(Xt))
 
     def cluster_report(self, X, *, block_rows: int | None = None) -> ClusterReport:
         """Per-cluster quality of ``X`` under the fitted centres, a :class:`ClusterReport`:
@@ -401,14 +392,12 @@ class _Serving(_Params):
         A row's cluster is :meth:`predict_topk`'s first column: the exact nearest centre, the
         lower index on ties.  For bfloat16 that can differ from :meth:`predict` on near-ties,
         which ranks by packed keys.  Cosine models report on unit rows.  numpy in, numpy out."""
-        from . import ops
-
         self._check_fitted()
         c = self.cluster_centers_
 
         def fold(table):
-            self._fold_blocks(X, lambda Xt, pk: ops.quality_rows(table, Xt, c, pack=pk, block_rows=block_rows),
-                              block_rows)
+            for _, Xt, pk in self._host_blocks(X, block_rows):
+                ops.quality_rows(table, Xt, c, pack=pk, block_rows=block_rows)
 
         rep = _report_table(c, getattr(self, "comm", None) or get_comm(), self.dtype, fold)
         return rep if torch.is_tensor(X) else rep.numpy()
@@ -436,19 +425,12 @@ class _Serving(_Params):
         centre, the lower index on ties, as in :meth:`cluster_report`.  For bfloat16 that can
         differ from :meth:`predict` on near-ties, which ranks by packed keys.  Rows whose
         distance is NaN or infinite are in no list.  numpy in, numpy out."""
-        from . import ops
-
         self._check_fitted()
         c = self.cluster_centers_
 
         def fold(table):
-            seen = [0]
-
-            def run(Xt, pk):
-                ops.exemplar_rows(table, Xt, c, row0=seen[0], farthest=farthest, pack=pk, block_rows=block_rows)
-                seen[0] += Xt.shape[0]
-
-            self._fold_blocks(X, run, block_rows)
+            for start, Xt, pk in self._host_blocks(X, block_rows):
+                ops.exemplar_rows(table, Xt, c, row0=start, farthest=farthest, pack=pk, block_rows=block_rows)
 
         rows, d = _exemplar_lists(c.shape[0], m, c.device, getattr(self, "comm", None) or get_comm(),
                                   X.shape[0], farthest, squared, fold)
@@ -477,16 +459,13 @@ class _Serving(_Params):
         A row's cluster and distance are :meth:`predict_topk`'s first column: the exact nearest
         centre, the lower index on ties, as in :meth:`cluster_report`.  Rows whose distance is NaN
         or infinite are not counted.  numpy in, numpy out."""
-        from . import ops
-
         self._check_fitted()
         c = self.cluster_centers_
         qs = ops.quantile_levels(q)
         chunks = []
-        self._fold_blocks(
-            X, lambda Xt, pk: chunks.extend(ops.quantile_top1(Xt, c, pack=pk, block_rows=block_rows)), block_rows)
-        comm = getattr(self, "comm", None) or get_comm()
-        reduce = comm.allreduce_ if comm is not None and comm.grouped else None
+        for _, Xt, pk in self._host_blocks(X, block_rows):
+            chunks.extend(ops.quantile_top1(Xt, c, pack=pk, block_rows=block_rows))
+        reduce = _allreduce(getattr(self, "comm", None) or get_comm())
         v, counts = ops.quantile_passes(chunks, c.shape[0], qs, c.device, reduce=reduce)
         v = v if squared else v.sqrt()
         return (v, counts) if torch.is_tensor(X) else (v.cpu().numpy(), counts.cpu().numpy())
@@ -495,8 +474,6 @@ class _Serving(_Params):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine
         metric, between unit rows and unit centres: sqrt(2 - 2 cos)).  On the GPU: the MFMA
         transform kernel on the serving pack (csrc/transform.hip)."""
-        from . import ops
-
         self._check_fitted()
         Xt, was_numpy = self._inputs(X)
         d = ops.transform(Xt, self.cluster_centers_, pack=self._serving_pack(Xt))
@@ -1280,28 +1257,27 @@ def fit(X, k: int, **kw):
     return km._out(km.cluster_centers_), km._out(km.labels_)
 
 
-def predict(X, centers, dtype="float32"):
-    """Nearest-centre labels of ``X`` for given ``centers``."""
-    from . import ops
-
-    was_numpy = not torch.is_tensor(X)
+def _given_centers(X, centers, dtype):
+    """The functional entry points' inputs: ``(Xt, c, was_numpy)``, the float32 centres on their
+    own device (the default device for array-likes) and ``X`` on it in ``dtype``."""
     c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
     dev = c.device if torch.is_tensor(centers) else _default_device(None)
-    Xt, _ = _to_tensor(X, dev, resolve_dtype(dtype))
-    labels, _ = ops.assign(Xt, c.to(dev), with_dist=False)
+    Xt, was_numpy = _to_tensor(X, dev, resolve_dtype(dtype))
+    return Xt, c.to(dev), was_numpy
+
+
+def predict(X, centers, dtype="float32"):
+    """Nearest-centre labels of ``X`` for given ``centers``."""
+    Xt, c, was_numpy = _given_centers(X, centers, dtype)
+    labels, _ = ops.assign(Xt, c, with_dist=False)
     return labels.cpu().numpy() if was_numpy else labels
 
 
 def predict_topk(X, centers, m: int, dtype="float32"):
     """The ``m`` nearest of the given ``centers`` for every row of ``X``: ``(labels [n, m],
     Euclidean distances [n, m])``, nearest first (``KMeans.predict_topk`` without a model)."""
-    from . import ops
-
-    was_numpy = not torch.is_tensor(X)
-    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
-    dev = c.device if torch.is_tensor(centers) else _default_device(None)
-    Xt, _ = _to_tensor(X, dev, resolve_dtype(dtype))
-    idx, d2 = ops.topk(Xt, c.to(dev), m)
+    Xt, c, was_numpy = _given_centers(X, centers, dtype)
+    idx, d2 = ops.topk(Xt, c, m)
     d = d2.sqrt()
     return (idx.cpu().numpy(), d.cpu().numpy()) if was_numpy else (idx, d)
 
@@ -1309,15 +1285,8 @@ def predict_topk(X, centers, m: int, dtype="float32"):
 def cluster_report(X, centers, dtype="float32") -> ClusterReport:
     """Per-cluster quality of ``X`` under the given ``centers``
     (``KMeans.cluster_report`` without a model; with a process group ``X`` is the rank's shard)."""
-    from . import ops
-
-    was_numpy = not torch.is_tensor(X)
-    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
-    dev = c.device if torch.is_tensor(centers) else _default_device(None)
-    dt = resolve_dtype(dtype)
-    Xt, _ = _to_tensor(X, dev, dt)
-    c = c.to(dev)
-    rep = _report_table(c, get_comm(), dt, lambda table: ops.quality_rows(table, Xt, c))
+    Xt, c, was_numpy = _given_centers(X, centers, dtype)
+    rep = _report_table(c, get_comm(), resolve_dtype(dtype), lambda table: ops.quality_rows(table, Xt, c))
     return rep.numpy() if was_numpy else rep
 
 
@@ -1326,14 +1295,8 @@ def cluster_exemplars(X, centers, m: int, dtype="float32", farthest: bool = Fals
     from it) among the rows assigned to it: ``(rows [K, m], Euclidean distances [K, m])``
     (``KMeans.cluster_exemplars`` without a model; with a process group ``X`` is the rank's shard
     and the rows are global indices)."""
-    from . import ops
-
-    was_numpy = not torch.is_tensor(X)
-    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
-    dev = c.device if torch.is_tensor(centers) else _default_device(None)
-    Xt, _ = _to_tensor(X, dev, resolve_dtype(dtype))
-    c = c.to(dev)
-    rows, d = _exemplar_lists(c.shape[0], m, dev, get_comm(), Xt.shape[0], farthest, False,
+    Xt, c, was_numpy = _given_centers(X, centers, dtype)
+    rows, d = _exemplar_lists(c.shape[0], m, c.device, get_comm(), Xt.shape[0], farthest, False,
                               lambda table: ops.exemplar_rows(table, Xt, c, farthest=farthest))
     return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
 
@@ -1342,15 +1305,8 @@ def cluster_quantiles(X, centers, q, dtype="float32"):
     """Exact per-cluster quantiles of the Euclidean distances of the rows of ``X`` to the nearest
     of the given ``centers``: ``(values [K, Q], counts [K])`` (``KMeans.cluster_quantiles`` without
     a model; with a process group ``X`` is the rank's shard)."""
-    from . import ops
-
-    was_numpy = not torch.is_tensor(X)
-    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
-    dev = c.device if torch.is_tensor(centers) else _default_device(None)
-    Xt, _ = _to_tensor(X, dev, resolve_dtype(dtype))
-    comm = get_comm()
-    v, counts = ops.cluster_quantiles(Xt, c.to(dev), q,
-                                      reduce=comm.allreduce_ if comm is not None and comm.grouped else None)
+    Xt, c, was_numpy = _given_centers(X, centers, dtype)
+    v, counts = ops.cluster_quantiles(Xt, c, q, reduce=_allreduce(get_comm()))
     v = v.sqrt()
     return (v.cpu().numpy(), counts.cpu().numpy()) if was_numpy else (v, counts)
 

@@ -207,20 +207,30 @@ void check_i64(const Tensor& t, const char* name, int64_t numel_min) {
   TORCH_CHECK(t.numel() >= numel_min, "mikmeans: ", name, " too small");
 }
 
-void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {
-  TORCH_CHECK(idx.dim() == 2 && d2.dim() == 2 && idx.size(0) == d2.size(0) && idx.size(1) == d2.size(1),
-              "mikmeans: idx and d2 must both be [N, m]");
+// The inputs every fold over the top-k output shares (csrc/fold.h): idx int32 and d2 float32,
+// both contiguous [N, m] with m >= 1, and a contiguous int64 table of at least table_min words
+// and at most INT32_MAX clusters on their device.  Returns {N, m}, m the row stride.
+std::pair<int64_t, int64_t> check_fold(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t table_min) {
+  TORCH_CHECK(idx.dim() == 2 && d2.dim() == 2 && idx.size(0) == d2.size(0) && idx.size(1) == d2.size(1) &&
+                  idx.size(1) >= 1,
+              "mikmeans: idx and d2 must both be [N, m] with m >= 1");
   const int64_t N = idx.size(0), m = idx.size(1);
-  TORCH_CHECK(m == 1 || m == 2, "mikmeans: quality_accumulate needs m = 1 or 2, got ", m);
   check_i32(idx, "idx", N * m);
   check_f32(d2, "d2", N * m);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(d2.data_ptr()) % 8 == 0, "mikmeans: d2 must be 8-B aligned");
-  TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUALITY_WORDS, "mikmeans: table must be [K, ",
-              mk::QUALITY_WORDS, "]");
-  check_i64(table, "table", mk::QUALITY_WORDS);
-  TORCH_CHECK(table.size(0) <= INT32_MAX, "mikmeans: too many clusters");
+  TORCH_CHECK(table.dim() >= 1, "mikmeans: table must be [K, ...]");
+  check_i64(table, "table", table_min);
+  TORCH_CHECK(table.size(0) <= INT32_MAX && m <= INT32_MAX, "mikmeans: too many clusters");
   TORCH_CHECK(idx.get_device() == table.get_device() && d2.get_device() == table.get_device(),
               "mikmeans: idx, d2 and table must share a device");
+  return {N, m};
+}
+
+void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {
+  TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUALITY_WORDS, "mikmeans: table must be [K, ",
+              mk::QUALITY_WORDS, "]");
+  const auto [N, m] = check_fold(idx, d2, table, mk::QUALITY_WORDS);
+  TORCH_CHECK(m == 1 || m == 2, "mikmeans: quality_accumulate needs m = 1 or 2, got ", m);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(d2.data_ptr()) % 8 == 0, "mikmeans: d2 must be 8-B aligned");
   mk::QualityArgs a;
   a.idx = idx.data_ptr<int32_t>(); a.dist = d2.data_ptr<float>(); a.N = N; a.m = (int)m;
   a.K = (int)table.size(0);
@@ -233,18 +243,9 @@ void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table
 
 void exemplar_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t row0, bool farthest,
                          int64_t path) {
-  TORCH_CHECK(idx.dim() == 2 && d2.dim() == 2 && idx.size(0) == d2.size(0) && idx.size(1) == d2.size(1) &&
-                  idx.size(1) >= 1,
-              "mikmeans: idx and d2 must both be [N, m_topk]");
-  const int64_t N = idx.size(0), mt = idx.size(1);
-  check_i32(idx, "idx", N * mt);
-  check_f32(d2, "d2", N * mt);
   TORCH_CHECK(table.dim() == 2 && table.size(1) >= 1 && table.size(1) <= mk::EXEMPLAR_MAX,
               "mikmeans: table must be [K, m] with 1 <= m <= ", mk::EXEMPLAR_MAX);
-  check_i64(table, "table", 1);
-  TORCH_CHECK(table.size(0) <= INT32_MAX && mt <= INT32_MAX, "mikmeans: too many clusters");
-  TORCH_CHECK(idx.get_device() == table.get_device() && d2.get_device() == table.get_device(),
-              "mikmeans: idx, d2 and table must share a device");
+  const auto [N, mt] = check_fold(idx, d2, table, 1);
   TORCH_CHECK(row0 >= 0 && row0 + N <= (int64_t(1) << 32),
               "mikmeans: exemplar_accumulate takes row indices below 2^32 (row0 + N)");
   mk::ExemplarArgs a;
@@ -260,19 +261,10 @@ void exemplar_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& tabl
 
 void quantile_hist(const Tensor& idx, const Tensor& d2, const Tensor& table, const c10::optional<Tensor>& prefix,
                    int64_t pass, int64_t path, int64_t agg) {
-  TORCH_CHECK(idx.dim() == 2 && d2.dim() == 2 && idx.size(0) == d2.size(0) && idx.size(1) == d2.size(1) &&
-                  idx.size(1) >= 1,
-              "mikmeans: idx and d2 must both be [N, m_topk]");
-  const int64_t N = idx.size(0), mt = idx.size(1);
-  check_i32(idx, "idx", N * mt);
-  check_f32(d2, "d2", N * mt);
   TORCH_CHECK(pass >= 0 && pass < mk::QUANTILE_PASSES, "mikmeans: quantile_hist pass must be 0..3, got ", pass);
   TORCH_CHECK(table.dim() == (pass == 0 ? 2 : 3) && table.size(-1) == mk::QUANTILE_BINS,
               "mikmeans: table must be [K, 256] in pass 0 and [K, Q, 256] in passes 1..3");
-  check_i64(table, "table", 1);
-  TORCH_CHECK(table.size(0) <= INT32_MAX && mt <= INT32_MAX, "mikmeans: too many clusters");
-  TORCH_CHECK(idx.get_device() == table.get_device() && d2.get_device() == table.get_device(),
-              "mikmeans: idx, d2 and table must share a device");
+  const auto [N, mt] = check_fold(idx, d2, table, 1);
   mk::QuantileHistArgs a;
   a.idx = idx.data_ptr<int32_t>(); a.dist = d2.data_ptr<float>(); a.N = N; a.mt = (int)mt;
   a.K = (int)table.size(0); a.Q = 1; a.pass = (int)pass; a.prefix = nullptr;
@@ -956,10 +948,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quality_uses_lds", [](int64_t N, int64_t K) { return mk::quality_uses_lds(N, (int)K); },
         "whether a batch of N rows over K labels takes the LDS-private kernel");
   m.attr("QUALITY_WORDS") = mk::QUALITY_WORDS;
-  m.attr("QUALITY_PASS_ROWS") = (int64_t)mk::QUALITY_MAX_BLOCKS * mk::QUALITY_THREADS;
-  m.attr("QUALITY_LDS_PASS_ROWS") = (int64_t)mk::QUALITY_LDS_BLOCKS * mk::QUALITY_LDS_THREADS;
+  m.attr("QUALITY_PASS_ROWS") = (int64_t)mk::FOLD_MAX_BLOCKS * mk::FOLD_THREADS;
+  m.attr("QUALITY_LDS_PASS_ROWS") = (int64_t)mk::FOLD_LDS_BLOCKS * mk::FOLD_LDS_THREADS;
   m.attr("QUALITY_LDS_MAX_K") = mk::QUALITY_LDS_MAX_K;
-  m.attr("QUALITY_LDS_MIN_ROWS") = mk::QUALITY_LDS_MIN_ROWS;
+  m.attr("QUALITY_LDS_MIN_ROWS") = mk::FOLD_LDS_MIN_ROWS;
   m.def("exemplar_accumulate", &exemplar_accumulate,
         "min-insert the top-1 output's rows into the per-cluster exemplar table [K, m] (64-bit integer atomic min)",
         py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("row0") = 0, py::arg("farthest") = false,
@@ -968,7 +960,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "whether a batch of N rows over K lists of m takes the LDS-private kernel");
   m.attr("EXEMPLAR_MAX") = mk::EXEMPLAR_MAX;
   m.attr("EXEMPLAR_LDS_MAX_WORDS") = mk::EXEMPLAR_LDS_MAX_WORDS;
-  m.attr("EXEMPLAR_LDS_MIN_ROWS") = mk::EXEMPLAR_LDS_MIN_ROWS;
+  m.attr("EXEMPLAR_LDS_MIN_ROWS") = mk::FOLD_LDS_MIN_ROWS;
   m.attr("EXEMPLAR_LDS_RULE_KMM") = mk::EXEMPLAR_LDS_RULE_KMM;
   m.def("quantile_hist", &quantile_hist,
         "add the top-1 output's rows into one radix-select pass's per-cluster digit histogram (64-bit integer atomic add)",
@@ -989,7 +981,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("QUANTILE_MAX_Q") = mk::QUANTILE_MAX_Q;
   m.attr("QUANTILE_BINS") = mk::QUANTILE_BINS;
   m.attr("QUANTILE_LDS_MAX_LISTS") = mk::QUANTILE_LDS_MAX_LISTS;
-  m.attr("QUANTILE_LDS_MIN_ROWS") = mk::QUANTILE_LDS_MIN_ROWS;
+  m.attr("QUANTILE_LDS_MIN_ROWS") = mk::FOLD_LDS_MIN_ROWS;
   m.attr("QUANTILE_AGG_ROUNDS") = mk::QUANTILE_AGG_ROUNDS;
   m.attr("QUANTILE_LDS_AGG_ROUNDS") = mk::QUANTILE_LDS_AGG_ROUNDS;
   m.def("reduce_cols", &reduce_cols,"lo sums of the wide-range columns (residual pass)");

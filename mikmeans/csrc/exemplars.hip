@@ -31,18 +31,19 @@
 // costs at most m atomics; there is no lock, no spin and no retry loop.  (A key that meets
 // itself in a slot stops: accumulating the same rows twice changes nothing.)
 //
-// Two kernels, the same table.  exemplar_kernel inserts every row straight into the global
-// table (64-bit global atomic min; after the lists have warmed up almost every row is turned
-// away by the read of L[m-1]).  exemplar_lds_kernel (K * m <= EXEMPLAR_LDS_MAX_WORDS) keeps a
-// private [K][m] table in the workgroup's LDS (up to 160 KiB, one 1024-thread workgroup per
-// CU), inserts its rows there with the same chain on LDS atomics and then inserts every
-// non-empty entry into the global table with the same filtered chain.  The m smallest of a
-// union are the m smallest of the parts' m smallest, so both give the same table bit for bit.
+// One kernel, two forms (fold.h), the same table.  The global form inserts every row straight
+// into the global table (64-bit global atomic min; after the lists have warmed up almost every
+// row is turned away by the read of L[m-1]).  The LDS form (K * m <= EXEMPLAR_LDS_MAX_WORDS)
+// keeps a private [K][m] table in the workgroup's LDS, inserts its rows there with the same
+// chain on LDS atomics and then inserts every non-empty entry into the global table with the
+// same filtered chain.  The m smallest of a union are the m smallest of the parts' m smallest,
+// so both give the same table bit for bit.
 // Measured (profiles/r7_02_exemplars.md): the flush is K * m inserts of up to m steps per
 // workgroup on lists that all workgroups share, so the LDS form wins for short lists and few
 // clusters (where the global form's rows contend on few lists) and loses beyond; the launcher
 // takes it for K * m^2 <= EXEMPLAR_LDS_RULE_KMM.
 #include "common.h"
+#include "fold.h"
 #include "kernels.h"
 
 namespace mk {
@@ -64,51 +65,46 @@ __device__ __forceinline__ void exemplar_insert(unsigned long long* L, int m, un
 
 // The key of row `row` (already offset by row0) at squared distance d2; false: the row is in no list.
 __device__ __forceinline__ bool exemplar_key(float d2, unsigned row, int farthest, unsigned long long& key) {
-  if (!(fabsf(d2) < __builtin_inff())) return false;   // NaN or +-inf
-  const float a2 = d2 > 0.0f ? d2 : 0.0f;              // (-0 counts as +0)
-  const unsigned bits = __float_as_uint(a2);
+  if (!fold_finite(d2)) return false;
+  const unsigned bits = fold_bits(d2);
   const unsigned hi = farthest ? 0x7F7FFFFFu - bits : bits;
   key = ((unsigned long long)hi << 32) | row;
   return true;
 }
 
-__global__ __launch_bounds__(EXEMPLAR_THREADS) void exemplar_kernel(ExemplarArgs a) {
-  const int64_t stride = (int64_t)gridDim.x * EXEMPLAR_THREADS;
-  for (int64_t row = (int64_t)blockIdx.x * EXEMPLAR_THREADS + threadIdx.x; row < a.N; row += stride) {
-    const int k = a.idx[row * a.mt];
-    if ((unsigned)k >= (unsigned)a.K) continue;
-    unsigned long long key;
-    if (!exemplar_key(a.dist[row * a.mt], a.row0 + (unsigned)row, a.farthest, key)) continue;
-    exemplar_insert(a.table + (int64_t)k * a.m, a.m, key);
-  }
-}
-
-__global__ __launch_bounds__(EXEMPLAR_LDS_THREADS) void exemplar_lds_kernel(ExemplarArgs a) {
+template <bool LDS>
+__global__ __launch_bounds__(LDS ? FOLD_LDS_THREADS : FOLD_THREADS) void exemplar_kernel(ExemplarArgs a) {
+  constexpr int THREADS = LDS ? FOLD_LDS_THREADS : FOLD_THREADS;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* t = reinterpret_cast<unsigned long long*>(smem);   // [K][m]
+  unsigned long long* t = reinterpret_cast<unsigned long long*>(smem);   // LDS: [K][m]
   const int nw = a.K * a.m;
-  for (int i = threadIdx.x; i < nw; i += EXEMPLAR_LDS_THREADS) t[i] = EXEMPLAR_EMPTY;
-  __syncthreads();
-  const int64_t stride = (int64_t)gridDim.x * EXEMPLAR_LDS_THREADS;
-  for (int64_t row = (int64_t)blockIdx.x * EXEMPLAR_LDS_THREADS + threadIdx.x; row < a.N; row += stride) {
+  if (LDS) {
+    for (int i = threadIdx.x; i < nw; i += THREADS) t[i] = EXEMPLAR_EMPTY;
+    __syncthreads();
+  }
+  const int64_t stride = (int64_t)gridDim.x * THREADS;
+  for (int64_t row = (int64_t)blockIdx.x * THREADS + threadIdx.x; row < a.N; row += stride) {
     const int k = a.idx[row * a.mt];
     if ((unsigned)k >= (unsigned)a.K) continue;
     unsigned long long key;
     if (!exemplar_key(a.dist[row * a.mt], a.row0 + (unsigned)row, a.farthest, key)) continue;
-    exemplar_insert(t + k * a.m, a.m, key);
+    // (the LDS index stays 32-bit arithmetic)
+    exemplar_insert(LDS ? t + k * a.m : a.table + (int64_t)k * a.m, a.m, key);
   }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nw; i += EXEMPLAR_LDS_THREADS) {
-    const unsigned long long v = t[i];
-    if (v == EXEMPLAR_EMPTY) continue;
-    const int k = i / a.m;
-    exemplar_insert(a.table + (int64_t)k * a.m, a.m, v);
+  if (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nw; i += THREADS) {
+      const unsigned long long v = t[i];
+      if (v == EXEMPLAR_EMPTY) continue;
+      const int k = i / a.m;
+      exemplar_insert(a.table + (int64_t)k * a.m, a.m, v);
+    }
   }
 }
 
 bool exemplar_uses_lds(int64_t N, int K, int m) {
   return (int64_t)K * m <= EXEMPLAR_LDS_MAX_WORDS && (int64_t)K * m * m <= EXEMPLAR_LDS_RULE_KMM &&
-         N >= EXEMPLAR_LDS_MIN_ROWS;
+         N >= FOLD_LDS_MIN_ROWS;
 }
 
 hipError_t launch_exemplars(const ExemplarArgs& a, hipStream_t s, int path) {
@@ -118,21 +114,14 @@ hipError_t launch_exemplars(const ExemplarArgs& a, hipStream_t s, int path) {
   const bool fits = (int64_t)a.K * a.m <= EXEMPLAR_LDS_MAX_WORDS;
   if (path > 0 && !fits) return hipErrorInvalidValue;
   if (path < 0 ? exemplar_uses_lds(a.N, a.K, a.m) : path > 0) {
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)exemplar_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024);
-      attr = true;
-    }
-    const int64_t want = (a.N + 4 * EXEMPLAR_LDS_THREADS - 1) / (4 * EXEMPLAR_LDS_THREADS);   // >= 4 rows a thread
-    const unsigned nb = (unsigned)(want < EXEMPLAR_LDS_BLOCKS ? want : EXEMPLAR_LDS_BLOCKS);
-    const size_t lds = (size_t)a.K * a.m * sizeof(unsigned long long);
-    hipLaunchKernelGGL(exemplar_lds_kernel, dim3(nb), dim3(EXEMPLAR_LDS_THREADS), lds, s, a);
-    return hipGetLastError();
+    fold_lds_optin<exemplar_kernel<true>>();
+    const unsigned nb = fold_grid(a.N, FOLD_LDS_THREADS, FOLD_LDS_ROWS, FOLD_LDS_BLOCKS);
+    const size_t bytes = (size_t)a.K * a.m * sizeof(unsigned long long);
+    hipLaunchKernelGGL(exemplar_kernel<true>, dim3(nb), dim3(FOLD_LDS_THREADS), bytes, s, a);
+  } else {
+    const unsigned nb = fold_grid(a.N, FOLD_THREADS, 1, FOLD_MAX_BLOCKS);
+    hipLaunchKernelGGL(exemplar_kernel<false>, dim3(nb), dim3(FOLD_THREADS), 0, s, a);
   }
-  const int64_t want = (a.N + EXEMPLAR_THREADS - 1) / EXEMPLAR_THREADS;
-  const unsigned nb = (unsigned)(want < EXEMPLAR_MAX_BLOCKS ? want : EXEMPLAR_MAX_BLOCKS);
-  hipLaunchKernelGGL(exemplar_kernel, dim3(nb), dim3(EXEMPLAR_THREADS), 0, s, a);
   return hipGetLastError();
 }
 

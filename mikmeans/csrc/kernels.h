@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "fold.h"   // the frame constants of the per-cluster folds (FOLD_*)
+
 namespace mk {
 
 enum DType : int { DT_F32 = 0, DT_BF16 = 1 };
@@ -125,15 +127,10 @@ hipError_t launch_topk(int dtype, int dpad, const TopkArgs& a, hipStream_t s);
 // into) with integer atomics: per label the digits of sum a^2 and the row count, the digits of
 // sum a, the non-finite rows, the fixed-point simplified-silhouette sum and the largest a^2.
 constexpr int QUALITY_WORDS = 24;
-constexpr int QUALITY_THREADS = 256;
-constexpr int QUALITY_MAX_BLOCKS = 2048;   // rows past QUALITY_MAX_BLOCKS * QUALITY_THREADS: the grid-stride loop
-// The LDS-private form: words 0..17 of every label in one workgroup's LDS (<= 160 KiB), one
-// 1024-thread workgroup per CU, taken for K <= QUALITY_LDS_MAX_K and N >= QUALITY_LDS_MIN_ROWS.
+// The LDS-private form (fold.h): words 0..17 of every label in the workgroup's LDS, taken for
+// K <= QUALITY_LDS_MAX_K and N >= FOLD_LDS_MIN_ROWS.
 constexpr int QUALITY_LDS_WORDS = 18;
-constexpr int QUALITY_LDS_THREADS = 1024;
-constexpr int QUALITY_LDS_BLOCKS = 256;
-constexpr int QUALITY_LDS_MAX_K = 160 * 1024 / (QUALITY_LDS_WORDS * 8);   // 1137
-constexpr int QUALITY_LDS_MIN_ROWS = 8192;
+constexpr int QUALITY_LDS_MAX_K = FOLD_LDS_BYTES / (QUALITY_LDS_WORDS * 8);   // 1137
 struct QualityArgs {
   const int32_t* idx;          // [N, m] centres, nearest first
   const float* dist;           // [N, m] their squared distances
@@ -149,18 +146,13 @@ hipError_t launch_quality(const QualityArgs& a, hipStream_t s, int path = -1);
 // min-inserted into): slot j of cluster k is the (j+1)-th smallest key hi << 32 | row of its rows,
 // hi = bits(a^2) (nearest) or 0x7F7FFFFF - bits(a^2) (farthest), row = row0 + the row's index.
 constexpr int EXEMPLAR_MAX = 64;             // longest list
-constexpr int EXEMPLAR_THREADS = 256;
-constexpr int EXEMPLAR_MAX_BLOCKS = 2048;    // rows past EXEMPLAR_MAX_BLOCKS * EXEMPLAR_THREADS: the grid-stride loop
-// The LDS-private form: a [K][m] table in one workgroup's LDS (<= 160 KiB), one 1024-thread
-// workgroup per CU; it holds K * m <= EXEMPLAR_LDS_MAX_WORDS.  The launcher's rule takes it for
-// K * m^2 <= EXEMPLAR_LDS_RULE_KMM and N >= EXEMPLAR_LDS_MIN_ROWS: its flush costs every
+// The LDS-private form (fold.h): a [K][m] table in the workgroup's LDS; it holds
+// K * m <= EXEMPLAR_LDS_MAX_WORDS.  The launcher's rule takes it for
+// K * m^2 <= EXEMPLAR_LDS_RULE_KMM and N >= FOLD_LDS_MIN_ROWS: its flush costs every
 // workgroup K * m inserts of up to m steps on lists all workgroups share, so it pays for short
 // lists and few clusters and loses to the global form beyond (profiles/r7_02_exemplars.md).
-constexpr int EXEMPLAR_LDS_THREADS = 1024;
-constexpr int EXEMPLAR_LDS_BLOCKS = 256;
-constexpr int EXEMPLAR_LDS_MAX_WORDS = 160 * 1024 / 8;   // 20480
+constexpr int EXEMPLAR_LDS_MAX_WORDS = FOLD_LDS_BYTES / 8;   // 20480
 constexpr int64_t EXEMPLAR_LDS_RULE_KMM = 16384;
-constexpr int64_t EXEMPLAR_LDS_MIN_ROWS = 8192;
 struct ExemplarArgs {
   const int32_t* idx;          // [N, mt] centres, nearest first (column 0 is read)
   const float* dist;           // [N, mt] their squared distances
@@ -182,19 +174,14 @@ hipError_t launch_exemplars(const ExemplarArgs& a, hipStream_t s, int path = -1)
 constexpr int QUANTILE_MAX_Q = 8;            // most quantiles in one call
 constexpr int QUANTILE_BINS = 256;           // one digit
 constexpr int QUANTILE_PASSES = 4;
-constexpr int QUANTILE_THREADS = 256;
-constexpr int QUANTILE_MAX_BLOCKS = 2048;    // rows past QUANTILE_MAX_BLOCKS * QUANTILE_THREADS: the grid-stride loop
-// The LDS-private form: a [lists][256] u32 table in one workgroup's LDS (<= 160 KiB), one
-// 1024-thread workgroup per CU; lists = K (pass 0) or K * Q (passes 1..3).  A launch takes fewer
+// The LDS-private form (fold.h): a [lists][256] u32 table in the workgroup's LDS;
+// lists = K (pass 0) or K * Q (passes 1..3).  A launch takes fewer
 // than 2^32 rows, so a u32 bin cannot wrap.  The launcher's rule takes it wherever the lists fit
-// and N >= QUANTILE_LDS_MIN_ROWS: measured (profiles/r7_03_quantiles.md) it is 3 to 200 times
+// and N >= FOLD_LDS_MIN_ROWS: measured (profiles/r7_03_quantiles.md) it is 3 to 200 times
 // faster in passes 0 and 1, 0.01 to 0.04 ms slower in passes 2 and 3 on distances without
 // ties (where it stays because equal distances put every row of a cluster on one global word),
 // and from 8192 rows on never more than 4 us behind.
-constexpr int QUANTILE_LDS_THREADS = 1024;
-constexpr int QUANTILE_LDS_BLOCKS = 256;
-constexpr int QUANTILE_LDS_MAX_LISTS = 160 * 1024 / (QUANTILE_BINS * 4);   // 160
-constexpr int64_t QUANTILE_LDS_MIN_ROWS = 8192;
+constexpr int QUANTILE_LDS_MAX_LISTS = FOLD_LDS_BYTES / (QUANTILE_BINS * 4);   // 160
 // The banded form: the same kernel for more lists than one workgroup's LDS holds.  Band b (the
 // grid's y) keeps lists [160 b, 160 b + 160) in LDS, reads every row and skips the rows of other
 // bands: ceil(lists / 160) sweeps over the 8 B rows instead of a global atomic per row.  It

@@ -19,26 +19,26 @@
 // The table is only ever added into: launches over row blocks accumulate.  Rows whose label is
 // outside [0, K) are skipped.  Mirror: mikmeans/ops/cpu.py quality_table.
 //
-// Two kernels, the same words.  quality_kernel adds every row straight into the global table:
-// ~9 scattered 8-byte atomics a row, each its own memory-side request.  quality_lds_kernel
-// (K <= QUALITY_LDS_MAX_K, batches of QUALITY_LDS_MIN_ROWS and more) keeps a private copy of
-// words 0..17 of every label in the workgroup's LDS (one 1024-thread workgroup per CU, up to
-// 160 KiB), adds its rows there with LDS integer atomics and flushes the non-zero words once at
-// the end, lane-contiguous: K * 18 global atomics per workgroup instead of 9 per row.  Integer
-// sums are associative, so both give the same table bit for bit.
+// One kernel, two forms (fold.h), the same words.  The global form adds every row straight into
+// the global table: ~9 scattered 8-byte atomics a row, each its own memory-side request.  The
+// LDS form (K <= QUALITY_LDS_MAX_K) keeps a private copy of words 0..17 of every label in the
+// workgroup's LDS, adds its rows there with LDS integer atomics and flushes the non-zero words
+// once at the end, lane-contiguous: K * 18 global atomics per workgroup instead of 9 per row.
+// Integer sums are associative, so both give the same table bit for bit.
 #include "common.h"
+#include "fold.h"
 #include "kernels.h"
 
 namespace mk {
 
 // One row's contribution to its label's words `w`.
 __device__ __forceinline__ void quality_row(unsigned long long* w, float a2f, float b2f, bool second) {
-  if (!(fabsf(a2f) < __builtin_inff())) {   // NaN or +-inf
+  if (!fold_finite(a2f)) {
     atomicAdd(w + 15, 1ull);
     return;
   }
-  const float a2c = a2f > 0.0f ? a2f : 0.0f;   // (the kernels clamp at +0; -0 must not reach the maximum)
-  const double a2 = (double)a2c;
+  const unsigned a2bits = fold_bits(a2f);         // (the clamp: -0 must not reach the maximum)
+  const double a2 = (double)__uint_as_float(a2bits);
   slot_add(w, a2, 1);
   slot_add(w + 8, __builtin_sqrt(a2), 0);
   if (second && b2f > 0.0f) {                  // (a NaN or zero b^2: s = 0)
@@ -51,14 +51,22 @@ __device__ __forceinline__ void quality_row(unsigned long long* w, float a2f, fl
     if (q) atomicAdd(w + 16, (unsigned long long)q);
   }
   // the word only grows, so a stale (smaller) read costs one redundant atomic, never a miss
-  const unsigned long long bits = __float_as_uint(a2c);
+  const unsigned long long bits = a2bits;
   if (bits > __hip_atomic_load(w + 17, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(w + 17, bits);
 }
 
-template <int M>
-__global__ __launch_bounds__(QUALITY_THREADS) void quality_kernel(QualityArgs a) {
-  const int64_t stride = (int64_t)gridDim.x * QUALITY_THREADS;
-  for (int64_t row = (int64_t)blockIdx.x * QUALITY_THREADS + threadIdx.x; row < a.N; row += stride) {
+template <int M, bool LDS>
+__global__ __launch_bounds__(LDS ? FOLD_LDS_THREADS : FOLD_THREADS) void quality_kernel(QualityArgs a) {
+  constexpr int THREADS = LDS ? FOLD_LDS_THREADS : FOLD_THREADS;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* t = reinterpret_cast<unsigned long long*>(smem);   // LDS: [K][QUALITY_LDS_WORDS]
+  const int nw = a.K * QUALITY_LDS_WORDS;
+  if (LDS) {
+    for (int i = threadIdx.x; i < nw; i += THREADS) t[i] = 0ull;
+    __syncthreads();
+  }
+  const int64_t stride = (int64_t)gridDim.x * THREADS;
+  for (int64_t row = (int64_t)blockIdx.x * THREADS + threadIdx.x; row < a.N; row += stride) {
     const int k = a.idx[row * M];
     if ((unsigned)k >= (unsigned)a.K) continue;
     float a2, b2 = 0.0f;
@@ -69,71 +77,43 @@ __global__ __launch_bounds__(QUALITY_THREADS) void quality_kernel(QualityArgs a)
     } else {
       a2 = a.dist[row];
     }
-    quality_row(a.table + (int64_t)k * QUALITY_WORDS, a2, b2, M == 2);
+    // (the LDS index stays 32-bit arithmetic)
+    quality_row(LDS ? t + k * QUALITY_LDS_WORDS : a.table + (int64_t)k * QUALITY_WORDS, a2, b2, M == 2);
   }
-}
-
-template <int M>
-__global__ __launch_bounds__(QUALITY_LDS_THREADS) void quality_lds_kernel(QualityArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* t = reinterpret_cast<unsigned long long*>(smem);   // [K][QUALITY_LDS_WORDS]
-  const int nw = a.K * QUALITY_LDS_WORDS;
-  for (int i = threadIdx.x; i < nw; i += QUALITY_LDS_THREADS) t[i] = 0ull;
-  __syncthreads();
-  const int64_t stride = (int64_t)gridDim.x * QUALITY_LDS_THREADS;
-  for (int64_t row = (int64_t)blockIdx.x * QUALITY_LDS_THREADS + threadIdx.x; row < a.N; row += stride) {
-    const int k = a.idx[row * M];
-    if ((unsigned)k >= (unsigned)a.K) continue;
-    float a2, b2 = 0.0f;
-    if (M == 2) {
-      const float2 d = reinterpret_cast<const float2*>(a.dist)[row];
-      a2 = d.x;
-      b2 = d.y;
-    } else {
-      a2 = a.dist[row];
+  if (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nw; i += THREADS) {
+      const unsigned long long v = t[i];
+      if (!v) continue;
+      const int k = i / QUALITY_LDS_WORDS, w = i - k * QUALITY_LDS_WORDS;
+      unsigned long long* g = a.table + (int64_t)k * QUALITY_WORDS + w;
+      if (w == 17) atomicMax(g, v); else atomicAdd(g, v);
     }
-    quality_row(t + k * QUALITY_LDS_WORDS, a2, b2, M == 2);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nw; i += QUALITY_LDS_THREADS) {
-    const unsigned long long v = t[i];
-    if (!v) continue;
-    const int k = i / QUALITY_LDS_WORDS, w = i - k * QUALITY_LDS_WORDS;
-    unsigned long long* g = a.table + (int64_t)k * QUALITY_WORDS + w;
-    if (w == 17) atomicMax(g, v); else atomicAdd(g, v);
   }
 }
 
 template <int M>
-static hipError_t launch_quality_lds(const QualityArgs& a, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)quality_lds_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    attr = true;
+static hipError_t launch_quality_m(const QualityArgs& a, hipStream_t s, bool lds) {
+  if (lds) {
+    fold_lds_optin<quality_kernel<M, true>>();
+    const unsigned nb = fold_grid(a.N, FOLD_LDS_THREADS, FOLD_LDS_ROWS, FOLD_LDS_BLOCKS);
+    const size_t bytes = (size_t)a.K * QUALITY_LDS_WORDS * sizeof(unsigned long long);
+    hipLaunchKernelGGL((quality_kernel<M, true>), dim3(nb), dim3(FOLD_LDS_THREADS), bytes, s, a);
+  } else {
+    const unsigned nb = fold_grid(a.N, FOLD_THREADS, 1, FOLD_MAX_BLOCKS);
+    hipLaunchKernelGGL((quality_kernel<M, false>), dim3(nb), dim3(FOLD_THREADS), 0, s, a);
   }
-  const int64_t want = (a.N + QUALITY_LDS_MIN_ROWS / 2 - 1) / (QUALITY_LDS_MIN_ROWS / 2);   // >= 4 rows a thread
-  const unsigned nb = (unsigned)(want < QUALITY_LDS_BLOCKS ? want : QUALITY_LDS_BLOCKS);
-  const size_t lds = (size_t)a.K * QUALITY_LDS_WORDS * sizeof(unsigned long long);
-  hipLaunchKernelGGL(quality_lds_kernel<M>, dim3(nb), dim3(QUALITY_LDS_THREADS), lds, s, a);
   return hipGetLastError();
 }
 
-bool quality_uses_lds(int64_t N, int K) { return K <= QUALITY_LDS_MAX_K && N >= QUALITY_LDS_MIN_ROWS; }
+bool quality_uses_lds(int64_t N, int K) { return K <= QUALITY_LDS_MAX_K && N >= FOLD_LDS_MIN_ROWS; }
 
 hipError_t launch_quality(const QualityArgs& a, hipStream_t s, int path) {
   if (a.N <= 0) return hipSuccess;
   if (a.K <= 0 || (a.m != 1 && a.m != 2)) return hipErrorInvalidValue;
   if (path > 0 && a.K > QUALITY_LDS_MAX_K) return hipErrorInvalidValue;
-  if (path < 0 ? quality_uses_lds(a.N, a.K) : path > 0)
-    return a.m == 2 ? launch_quality_lds<2>(a, s) : launch_quality_lds<1>(a, s);
-  const int64_t want = (a.N + QUALITY_THREADS - 1) / QUALITY_THREADS;
-  const unsigned nb = (unsigned)(want < QUALITY_MAX_BLOCKS ? want : QUALITY_MAX_BLOCKS);
-  if (a.m == 2)
-    hipLaunchKernelGGL(quality_kernel<2>, dim3(nb), dim3(QUALITY_THREADS), 0, s, a);
-  else
-    hipLaunchKernelGGL(quality_kernel<1>, dim3(nb), dim3(QUALITY_THREADS), 0, s, a);
-  return hipGetLastError();
+  const bool lds = path < 0 ? quality_uses_lds(a.N, a.K) : path > 0;
+  return a.m == 2 ? launch_quality_m<2>(a, s, lds) : launch_quality_m<1>(a, s, lds);
 }
 
 }  // namespace mk

@@ -38,10 +38,10 @@
 // count; lanes still pending after the rounds (diverse keys) add one each.  Integer sums are
 // associative, so every choice of `agg` gives the same table.
 //
-// Two kernels, the same table.  quantile_hist_kernel adds into the global table (64-bit global
-// atomic add).  quantile_hist_lds_kernel (lists = K or K * Q <= QUANTILE_LDS_MAX_LISTS) keeps a
-// private [lists][256] u32 table in the workgroup's LDS (up to 160 KiB, one 1024-thread
-// workgroup per CU), adds its rows there and flushes the non-zero bins with 64-bit global adds;
+// Two kernels on the frame of fold.h, the same table.  quantile_hist_kernel adds into the global
+// table (64-bit global atomic add).  quantile_hist_lds_kernel (lists = K or K * Q <=
+// QUANTILE_LDS_MAX_LISTS) keeps a private [lists][256] u32 table in the workgroup's LDS, adds
+// its rows there and flushes the non-zero bins with 64-bit global adds;
 // a launch takes fewer than 2^32 rows, so a u32 bin cannot wrap.  Past 160 lists the same kernel
 // runs banded: band b (the grid's y) holds lists [160 b, 160 b + 160), reads every row and skips
 // the rows of the other bands, so the rows are swept ceil(lists / 160) times.  Integer sums are
@@ -58,6 +58,7 @@
 // every wave on one cluster, and two rounds take pass 0 from 0.74 to 0.045 ms at K = 1024
 // (QUANTILE_AGG_ROUNDS = 2; more rounds only add to the later passes, whose digits differ).
 #include "common.h"
+#include "fold.h"
 #include "kernels.h"
 
 namespace mk {
@@ -100,10 +101,9 @@ __device__ __forceinline__ void quantile_rows(const QuantileHistArgs& a, T* t, i
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const float d2 = dd[u];
-      const bool ok = (unsigned)kk[u] < (unsigned)a.K && fabsf(d2) < __builtin_inff();   // (NaN and +-inf: no)
+      const bool ok = (unsigned)kk[u] < (unsigned)a.K && fold_finite(dd[u]);
       const unsigned k = ok ? (unsigned)kk[u] : 0u;
-      const unsigned bits = __float_as_uint(d2 > 0.0f ? d2 : 0.0f);                      // (-0 counts as +0)
+      const unsigned bits = fold_bits(dd[u]);
       if (a.pass == 0) {
         const unsigned slot = k - list0;
         const bool hit = ok && slot < nlists;
@@ -120,24 +120,24 @@ __device__ __forceinline__ void quantile_rows(const QuantileHistArgs& a, T* t, i
   }
 }
 
-__global__ __launch_bounds__(QUANTILE_THREADS) void quantile_hist_kernel(QuantileHistArgs a) {
-  quantile_rows(a, a.table, QUANTILE_THREADS, 0u, (unsigned)quantile_lists(a.K, a.Q, a.pass));
+__global__ __launch_bounds__(FOLD_THREADS) void quantile_hist_kernel(QuantileHistArgs a) {
+  quantile_rows(a, a.table, FOLD_THREADS, 0u, (unsigned)quantile_lists(a.K, a.Q, a.pass));
 }
 
 // Band blockIdx.y of the lists (one band when they fit a workgroup's LDS): see kernels.h.
-__global__ __launch_bounds__(QUANTILE_LDS_THREADS) void quantile_hist_lds_kernel(QuantileHistArgs a) {
+__global__ __launch_bounds__(FOLD_LDS_THREADS) void quantile_hist_lds_kernel(QuantileHistArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned* t = reinterpret_cast<unsigned*>(smem);   // [nlists][256]
   const unsigned lists = (unsigned)quantile_lists(a.K, a.Q, a.pass);
   const unsigned list0 = blockIdx.y * QUANTILE_LDS_MAX_LISTS;
   const unsigned nlists = lists - list0 < (unsigned)QUANTILE_LDS_MAX_LISTS ? lists - list0 : QUANTILE_LDS_MAX_LISTS;
   const int nw = (int)nlists * QUANTILE_BINS;
-  for (int i = threadIdx.x; i < nw; i += QUANTILE_LDS_THREADS) t[i] = 0u;
+  for (int i = threadIdx.x; i < nw; i += FOLD_LDS_THREADS) t[i] = 0u;
   __syncthreads();
-  quantile_rows(a, t, QUANTILE_LDS_THREADS, list0, nlists);
+  quantile_rows(a, t, FOLD_LDS_THREADS, list0, nlists);
   __syncthreads();
   unsigned long long* g = a.table + (int64_t)list0 * QUANTILE_BINS;
-  for (int i = threadIdx.x; i < nw; i += QUANTILE_LDS_THREADS) {
+  for (int i = threadIdx.x; i < nw; i += FOLD_LDS_THREADS) {
     const unsigned v = t[i];
     if (v) atomicAdd(g + i, (unsigned long long)v);
   }
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(QUANTILE_BINS) void quantile_select_kernel(Quantile
 }
 
 bool quantile_uses_lds(int64_t N, int64_t lists) {
-  return lists <= QUANTILE_LDS_MAX_LISTS && N >= QUANTILE_LDS_MIN_ROWS && N < (int64_t(1) << 32);
+  return lists <= QUANTILE_LDS_MAX_LISTS && N >= FOLD_LDS_MIN_ROWS && N < (int64_t(1) << 32);
 }
 
 int quantile_path(int64_t N, int64_t lists, int pass) {
@@ -217,26 +217,19 @@ hipError_t launch_quantile_hist(const QuantileHistArgs& args, hipStream_t s, int
   if ((path == 1 && bands > 1) || (path == 2 && bands > QUANTILE_BAND_LIMIT)) return hipErrorInvalidValue;
   if (path < 0) path = quantile_path(a.N, lists, a.pass);
   if (path > 0) {
-    static bool attr = false;
-    if (!attr) {
-      (void)hipFuncSetAttribute((const void*)quantile_hist_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024);
-      attr = true;
-    }
+    fold_lds_optin<quantile_hist_lds_kernel>();
     if (a.agg < 0) a.agg = QUANTILE_LDS_AGG_ROUNDS;
-    // one workgroup per CU over all bands, >= 4 rows a thread
-    const int64_t want = (a.N + 4 * QUANTILE_LDS_THREADS - 1) / (4 * QUANTILE_LDS_THREADS);
-    const int64_t most = QUANTILE_LDS_BLOCKS / bands > 0 ? QUANTILE_LDS_BLOCKS / bands : 1;
-    const unsigned nb = (unsigned)(want < most ? want : most);
+    // one workgroup per CU over all bands
+    const int64_t most = FOLD_LDS_BLOCKS / bands > 0 ? FOLD_LDS_BLOCKS / bands : 1;
+    const unsigned nb = fold_grid(a.N, FOLD_LDS_THREADS, FOLD_LDS_ROWS, most);
     const int64_t held = lists < QUANTILE_LDS_MAX_LISTS ? lists : QUANTILE_LDS_MAX_LISTS;
-    const size_t lds = (size_t)held * QUANTILE_BINS * sizeof(unsigned);
-    hipLaunchKernelGGL(quantile_hist_lds_kernel, dim3(nb, (unsigned)bands), dim3(QUANTILE_LDS_THREADS), lds, s, a);
+    const size_t bytes = (size_t)held * QUANTILE_BINS * sizeof(unsigned);
+    hipLaunchKernelGGL(quantile_hist_lds_kernel, dim3(nb, (unsigned)bands), dim3(FOLD_LDS_THREADS), bytes, s, a);
     return hipGetLastError();
   }
   if (a.agg < 0) a.agg = QUANTILE_AGG_ROUNDS;
-  const int64_t want = (a.N + QUANTILE_THREADS - 1) / QUANTILE_THREADS;
-  const unsigned nb = (unsigned)(want < QUANTILE_MAX_BLOCKS ? want : QUANTILE_MAX_BLOCKS);
-  hipLaunchKernelGGL(quantile_hist_kernel, dim3(nb), dim3(QUANTILE_THREADS), 0, s, a);
+  const unsigned nb = fold_grid(a.N, FOLD_THREADS, 1, FOLD_MAX_BLOCKS);
+  hipLaunchKernelGGL(quantile_hist_kernel, dim3(nb), dim3(FOLD_THREADS), 0, s, a);
   return hipGetLastError();
 }
 

@@ -335,7 +335,8 @@ def test_exemplars_are_world_size_invariant():
 
 
 def test_exemplar_kernel_resources(tmp_path):
-    """The built code object: both forms (global atomics, LDS-private) without scratch or spills."""
+    """The built code object: exemplar_kernel<LDS> in both forms (global atomics, LDS-private)
+    without scratch or spills."""
     from mikmeans import _build
     from mikmeans.utils import isa
 
@@ -345,7 +346,7 @@ def test_exemplar_kernel_resources(tmp_path):
     src = _build.CSRC / "exemplars.hip"
     obj = _build._compile(src, _build.source_flags(src.name), verbose=False)
     res = [r for r in isa.kernel_resources(isa.device_elf(obj, tmp_path / "exemplars.dev.o"))
-           if "exemplar_kernel" in r.name or "exemplar_lds_kernel" in r.name]
+           if "exemplar_kernel<" in r.name]
     assert len(res) == 2, [r.name for r in res]
     bad = [(r.name, r.vgprs, r.vgpr_spills, r.scratch_bytes) for r in res if r.vgpr_spills or r.scratch_bytes]
     assert not bad, bad

@@ -302,8 +302,8 @@ def test_report_is_world_size_invariant():
 
 
 def test_quality_kernel_resources(tmp_path):
-    """The built code object: both forms (global atomics, LDS-private), each for m = 1 and 2,
-    without scratch or spills."""
+    """The built code object: quality_kernel<M, LDS> in both forms (global atomics, LDS-private),
+    each for m = 1 and 2, without scratch or spills."""
     from mikmeans import _build
     from mikmeans.utils import isa
 
@@ -312,7 +312,8 @@ def test_quality_kernel_resources(tmp_path):
     assert "quality.hip" in _build.HIP_SOURCES
     src = _build.CSRC / "quality.hip"
     obj = _build._compile(src, _build.source_flags(src.name), verbose=False)
-    res = [r for r in isa.kernel_resources(isa.device_elf(obj, tmp_path / "quality.dev.o")) if "quality_kernel<" in r.name or "quality_lds_kernel<" in r.name]
+    res = [r for r in isa.kernel_resources(isa.device_elf(obj, tmp_path / "quality.dev.o"))
+           if "quality_kernel<" in r.name]
     assert len(res) == 4, [r.name for r in res]
     bad = [(r.name, r.vgprs, r.vgpr_spills, r.scratch_bytes) for r in res if r.vgpr_spills or r.scratch_bytes]
     assert not bad, bad

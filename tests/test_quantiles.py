@@ -4,6 +4,7 @@ the functional form, the CLI's ``report --quantiles`` and world-size invariance 
 (the GPU kernels against this mirror: test_gpu_quantiles.py)."""
 import json
 import os
+import shutil
 import subprocess
 import sys
 
@@ -262,3 +263,22 @@ def test_quantiles_are_world_size_invariant():
         for ov, oc in spawn_local(_ws_quantiles, world):
             assert torch.equal(oc, c)
             assert torch.equal(ov.view(torch.int32), v.view(torch.int32))     # (bits: NaN == NaN)
+
+
+def test_quantile_kernel_resources(tmp_path):
+    """The built code object: the two histogram kernels (global atomics, LDS-private) and the
+    select kernel, without scratch or spills."""
+    from mikmeans import _build
+    from mikmeans.utils import isa
+
+    if shutil.which(_build._hipcc()) is None and not os.path.exists(_build._hipcc()):
+        pytest.skip("hipcc not available")
+    assert "quantiles.hip" in _build.HIP_SOURCES
+    src = _build.CSRC / "quantiles.hip"
+    obj = _build._compile(src, _build.source_flags(src.name), verbose=False)
+    res = [r for r in isa.kernel_resources(isa.device_elf(obj, tmp_path / "quantiles.dev.o"))
+           if "quantile_" in r.name and "_kernel" in r.name]
+    names = sorted(r.name.split("(")[0].split("::")[-1] for r in res)
+    assert names == ["quantile_hist_kernel", "quantile_hist_lds_kernel", "quantile_select_kernel"], names
+    bad = [(r.name, r.vgprs, r.vgpr_spills, r.scratch_bytes) for r in res if r.vgpr_spills or r.scratch_bytes]
+    assert not bad, bad
