@@ -200,6 +200,22 @@ def _report_table(centers, comm, dtype, fold) -> ClusterReport:
     return ClusterReport.from_table(table, centers, dtype)
 
 
+def _merge_rank_lists(hi: torch.Tensor, rows: torch.Tensor, comm):
+    """Every rank's ``[L, m]`` lists of (key word, global row) pairs -- row -1 an empty slot -- merged
+    over the ranks of ``comm``: all-gathered, the m lexicographically smallest pairs kept per list.
+    ``(hi, rows)``, the same on every rank."""
+    L, m = rows.shape
+    last = 1 << 62                                            # (past every key word: they are below 2^31)
+    hi = torch.where(rows < 0, last, hi)
+    W = comm.world
+    hi = comm.all_gather(hi).permute(1, 0, 2).reshape(L, W * m)
+    rows = comm.all_gather(rows).permute(1, 0, 2).reshape(L, W * m)
+    o = torch.argsort(rows, dim=1, stable=True)               # by the global row, then (stable) by the key
+    hi, rows = hi.gather(1, o), rows.gather(1, o)             # word: the pairs in lexicographic order
+    o = torch.argsort(hi, dim=1, stable=True)[:, :m]
+    return hi.gather(1, o), rows.gather(1, o)
+
+
 def _exemplar_lists(K: int, m: int, device, comm, n_local: int, farthest: bool, squared: bool, fold):
     """``fold(table)`` min-inserts this rank's rows (indexed from 0) into an empty exemplar
     table; the lists are then merged over the ranks of ``comm`` -- every rank's ``[K, m]``
@@ -213,20 +229,92 @@ def _exemplar_lists(K: int, m: int, device, comm, n_local: int, farthest: bool, 
     if _allreduce(comm) is not None:
         _, start = _shard_info(int(n_local), comm, device)
         rows, _ = ops.exemplar_decode(table, row_start=start)
-        last = 1 << 62                                        # (past every key word: they are below 2^31)
-        hi = torch.where(rows < 0, last, table >> 32)
-        W = comm.world
-        hi = comm.all_gather(hi).permute(1, 0, 2).reshape(K, W * m)
-        rows = comm.all_gather(rows).permute(1, 0, 2).reshape(K, W * m)
-        o = torch.argsort(rows, dim=1, stable=True)           # by the global row, then (stable) by the key
-        hi, rows = hi.gather(1, o), rows.gather(1, o)         # word: the pairs in lexicographic order
-        o = torch.argsort(hi, dim=1, stable=True)[:, :m]
-        hi, rows = hi.gather(1, o), rows.gather(1, o)
+        hi, rows = _merge_rank_lists(table >> 32, rows, comm)
         bits = torch.where(rows < 0, 0, (0x7F7FFFFF - hi) if farthest else hi)
         d2 = torch.where(rows < 0, float("nan"), bits.to(torch.int32).view(torch.float32))
     else:
         rows, d2 = ops.exemplar_decode(table, farthest=farthest)
     return rows, (d2 if squared else d2.sqrt())
+
+
+def _merge_search_keys(keys: torch.Tensor, comm, row_start: int):
+    """This rank's sorted search keys ``[nq, m]`` decoded and merged over the ranks of ``comm``
+    (:func:`_merge_rank_lists`): ``(rows int64 [nq, m], d2 float32 [nq, m])``, the same on every rank."""
+    rows, d2 = ops.index_decode(keys, row_start=row_start)
+    if _allreduce(comm) is None:
+        return rows, d2
+    hi, rows = _merge_rank_lists(keys >> 32, rows, comm)
+    d2 = torch.where(rows < 0, float("nan"), torch.where(rows < 0, 0, hi).to(torch.int32).view(torch.float32))
+    return rows, d2
+
+
+class ClusterIndex:
+    """The rows of a dataset grouped by their nearest centre (an inverted-file index over the fitted
+    clusters), from :meth:`KMeans.build_index`.  ``n_rows``: the rows given (this rank's shard);
+    ``list_sizes`` (int64 [K]) and ``offsets`` (int64 [K + 1]): every list's length and where it
+    starts in ``order``; ``order``: the row ids, list after list and ascending within a list (rows
+    whose distance to their centre is not finite are in no list); ``nbytes``: what the index keeps
+    on its device.  In a multi-rank job the lists hold the rank's shard under global row ids."""
+
+    def __init__(self, model, index, row_start: int, comm):
+        self._model, self._index, self.row_start, self._comm = model, index, int(row_start), comm
+        self.n_rows = int(index.n)
+
+    @property
+    def offsets(self) -> torch.Tensor:
+        return self._index.offsets
+
+    @property
+    def list_sizes(self) -> torch.Tensor:
+        return self._index.offsets[1:] - self._index.offsets[:-1]
+
+    @property
+    def order(self) -> torch.Tensor:
+        return self._index.order[: int(self._index.offsets[-1])] + self.row_start
+
+    @property
+    def nbytes(self) -> int:
+        return self._index.nbytes
+
+    def rows_of(self, k: int) -> torch.Tensor:
+        """The row ids of cluster ``k``, ascending."""
+        K = self._index.K
+        if not 0 <= int(k) < K:
+            raise ValueError(f"rows_of needs 0 <= k < n_clusters ({K}), got k = {k}")
+        a, b = (int(v) for v in self._index.offsets[int(k) : int(k) + 2])
+        return self._index.order[a:b] + self.row_start
+
+    def search(self, Q, m: int, *, nprobe: int = 8, squared: bool = False):
+        """The ``m`` indexed rows nearest every query among the lists of its ``nprobe`` nearest
+        centres: ``(rows [nq, m] int64, distances [nq, m] float32)``, nearest first and equal
+        distances by the lower row id; a query whose probed lists hold fewer than ``m`` rows is
+        padded with row -1 and distance NaN.  ``1 <= m <= 32`` and ``1 <= nprobe <= n_clusters``;
+        ``nprobe = n_clusters`` is the exact brute-force search over the indexed rows.  Distances
+        are Euclidean as in :meth:`KMeans.transform` (``squared``: the kernel's squared values,
+        bitwise ``ops.transform(Q, X.float(), squared=True)``'s; cosine models work on unit rows).
+
+        On the GPU: the top-``nprobe`` kernel on the serving pack, a partition of the (query, probe)
+        pairs by list and the scan kernel of csrc/ivf.hip, one wave per (list, block of queries
+        probing it); a long list is not split over waves, so a single query runs one wave per
+        probed list.  Results are bitwise the same from run to run.  In a multi-rank job ``Q`` is
+        the same on every rank and every rank returns the one-rank result on the concatenated
+        shards.  Queries with non-finite coordinates give unspecified results.  numpy in, numpy
+        out; host queries bound for a GPU index go through in blocks."""
+        mdl = self._model
+        c = mdl.cluster_centers_
+        K = int(c.shape[0])
+        m, nprobe = int(m), int(nprobe)
+        if not 1 <= m <= ops.INDEX_MAX_M:
+            raise ValueError(f"search needs 1 <= m <= {ops.INDEX_MAX_M}, got m = {m}")
+        if not 1 <= nprobe <= K:
+            raise ValueError(f"search needs 1 <= nprobe <= n_clusters ({K}), got nprobe = {nprobe}")
+        if getattr(Q, "ndim", 2) != 2:
+            raise ValueError(f"Q must be 2-D [n_queries, n_features], got shape {tuple(Q.shape)}")
+        (keys,), was_numpy = mdl._row_blocks(
+            Q, lambda Qt, pk: (ops.index_search(self._index, Qt, c, m, nprobe, pack=pk),))
+        rows, d2 = _merge_search_keys(keys, self._comm, self.row_start)
+        d = d2 if squared else d2.sqrt()
+        return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
 
 
 class _Params:
@@ -469,6 +557,39 @@ class _Serving(_Params):
         v, counts = ops.quantile_passes(chunks, c.shape[0], qs, c.device, reduce=reduce)
         v = v if squared else v.sqrt()
         return (v, counts) if torch.is_tensor(X) else (v.cpu().numpy(), counts.cpu().numpy())
+
+    def build_index(self, X, *, block_rows: int | None = None) -> ClusterIndex:
+        """Index the rows of ``X`` by their nearest fitted centre, for :meth:`ClusterIndex.search`:
+        the fitted model as the coarse quantiser of an inverted-file (IVF-Flat) index.
+
+        A row's list is :meth:`predict_topk`'s first column (the exact nearest centre, the lower
+        index on ties, as in :meth:`cluster_report`); rows whose distance to it is NaN or infinite are
+        in no list; a list holds its rows in ascending row index.  Cosine models index unit rows.
+        On the GPU the rows are grouped by a native stable partition (csrc/ivf.hip: count, scan,
+        scatter; no atomic decides a position) and packed list after list in the layout the MFMA
+        kernels read centres in, each row read once in its own dtype.  The index is bitwise the
+        same from run to run and for any ``block_rows`` (rows per top-1 pass; host rows bound for
+        a GPU model are also copied in blocks of that size, twice: once for the lists, once for
+        the pack).  In a multi-rank job ``X`` is the rank's shard and row ids are global.  One index
+        takes fewer than 2^32 rows; on a GPU its memory plan (``memplan.plan_index``) is checked
+        against the HBM budget up front."""
+        self._check_fitted()
+        c = self.cluster_centers_
+        n = int(X.shape[0])
+        if n >= 1 << 32:
+            raise ValueError(f"build_index takes fewer than 2^32 rows, got {n}")
+        if c.is_cuda:
+            from .parallel import memplan
+
+            plan = memplan.plan_index(n, int(X.shape[1]), int(c.shape[0]), self.dtype, block_rows=block_rows)
+            plan.budget = memplan.hbm_budget(c.device)
+            if not plan.fits:
+                raise memplan.HBMCapacityError(f"build_index: {plan.summary()} does not fit")
+        comm = getattr(self, "comm", None) or get_comm()
+        start = _shard_info(n, comm, c.device)[1] if _allreduce(comm) is not None else 0
+        index = ops.index_build(None, c, block_rows=block_rows, n=n,
+                                blocks=lambda: self._host_blocks(X, block_rows))
+        return ClusterIndex(self, index, start, comm)
 
     def transform(self, X):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine
@@ -1309,6 +1430,22 @@ def cluster_quantiles(X, centers, q, dtype="float32"):
     v, counts = ops.cluster_quantiles(Xt, c, q, reduce=_allreduce(get_comm()))
     v = v.sqrt()
     return (v.cpu().numpy(), counts.cpu().numpy()) if was_numpy else (v, counts)
+
+
+class _GivenCenters(_Serving):
+    """The serving surface over given centres (the functional entry points that need a model)."""
+
+    def __init__(self, centers: torch.Tensor, dtype):
+        self.cluster_centers_, self.dtype = centers, dtype
+
+
+def build_index(X, centers, dtype="float32") -> ClusterIndex:
+    """Index the rows of ``X`` by the nearest of the given ``centers`` (``KMeans.build_index``
+    without a model; with a process group ``X`` is the rank's shard and the rows are global
+    indices)."""
+    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
+    dev = c.device if torch.is_tensor(centers) else _default_device(None)
+    return _GivenCenters(c.to(dev), resolve_dtype(dtype)).build_index(X)
 
 
 def fit_predict(X, k: int, **kw):

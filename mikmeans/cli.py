@@ -8,6 +8,8 @@ Commands (the reference's top-bar controls, app.mjs:240-288, as a CLI):
 * ``report``   -- per-cluster quality of a dataset under a saved model (sizes, inertia, radius,
                   simplified silhouette, Davies-Bouldin), as JSON; ``--exemplars M`` adds every
                   cluster's M nearest (``--farthest``: farthest) rows
+* ``search``   -- the M rows of a dataset nearest each query, through a saved model's clusters
+                  (``--nprobe P`` clusters searched per query; rows and distances as .npz)
 * ``blobs``    -- write a synthetic Gaussian-blob dataset
 * ``room``     -- the trait-card game headless: seed/populate/auto-assign/dashboard/export/import
 * ``session``  -- one participant of a live, replicated room session: found it (hosting the
@@ -173,6 +175,35 @@ def cmd_report(a) -> int:
         if a.output:
             Path(a.output).write_text(json.dumps(rep, indent=1))
         print(json.dumps({k: rep[k] for k in ("n_samples", "inertia", "silhouette", "davies_bouldin", "balance")}))
+    comm.close()
+    return 0
+
+
+def cmd_search(a) -> int:
+    """Nearest-row search through a saved model's clusters (``KMeans.build_index`` /
+    ``ClusterIndex.search``): every rank indexes its shard of ``--input``, all ranks search the same
+    ``--queries``, the per-rank lists are merged and rank 0 writes ``rows`` ([nq, M] int64, global
+    row indices, -1 padded) and ``distances`` ([nq, M] float32, NaN padded) to ``--output`` (.npz)."""
+    from . import KMeans, ops
+
+    from .utils.io import load_points
+
+    comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    km = KMeans.load(a.model, device=comm.device)
+    K = int(km.cluster_centers_.shape[0])
+    if not 1 <= a.top <= ops.INDEX_MAX_M:
+        raise SystemExit(f"search: --top must be in [1, {ops.INDEX_MAX_M}], got {a.top}")
+    if not 1 <= a.nprobe <= K:
+        raise SystemExit(f"search: --nprobe must be in [1, {K}], got {a.nprobe}")
+    X, n, start = load_points(a.input, comm.rank, comm.world)
+    Q = np.load(a.queries, allow_pickle=False)
+    index = km.build_index(X.to(comm.device))
+    rows, dist = index.search(Q, a.top, nprobe=a.nprobe, squared=a.squared)
+    if comm.rank == 0:
+        if a.output:
+            np.savez(a.output, rows=rows.astype(np.int64), distances=dist.astype(np.float32))
+        print(json.dumps({"n_samples": n, "n_queries": int(rows.shape[0]), "top": int(a.top), "nprobe": int(a.nprobe),
+                          "found": int((rows >= 0).sum())}))
     comm.close()
     return 0
 
@@ -445,6 +476,16 @@ def build_parser():
                     help="add every cluster's exact distance quantiles (1..8 values in [0, 1], e.g. 0.5,0.9,0.99) "
                          "to the written report")
     rp.add_argument("--device")
+    sp = sub.add_parser("search", help="the rows of a dataset nearest each query, through a saved model's clusters")
+    sp.add_argument("--model", required=True)
+    sp.add_argument("--input", required=True, help="the rows to index (.npy / .safetensors / .csv)")
+    sp.add_argument("--queries", required=True, help="the query rows (.npy)")
+    sp.add_argument("--top", type=int, required=True, metavar="M", help="rows per query (1..32)")
+    sp.add_argument("--nprobe", type=int, default=8, metavar="P",
+                    help="clusters searched per query (1..n_clusters; n_clusters = exact search)")
+    sp.add_argument("--squared", action="store_true", help="write squared distances")
+    sp.add_argument("--output", help="write rows and distances here (.npz)")
+    sp.add_argument("--device")
     b = sub.add_parser("blobs", help="write a synthetic dataset")
     b.add_argument("--n", type=int, required=True)
     b.add_argument("--d", type=int, required=True)
@@ -542,7 +583,7 @@ def main(argv=None) -> int:
         a, rest = la.parse_known_args(argv[1:])
         return cmd_launch(a, rest)
     a = build_parser().parse_args(argv)
-    return {"fit": cmd_fit, "predict": cmd_predict, "report": cmd_report, "blobs": cmd_blobs, "room": cmd_room, "session": cmd_session,
+    return {"fit": cmd_fit, "predict": cmd_predict, "report": cmd_report, "search": cmd_search, "blobs": cmd_blobs, "room": cmd_room, "session": cmd_session,
             "export": cmd_export, "import": cmd_import, "info": cmd_info, "plan": cmd_plan,
             "serve": cmd_serve}[a.cmd](a)
 

@@ -225,6 +225,90 @@ std::pair<int64_t, int64_t> check_fold(const Tensor& idx, const Tensor& d2, cons
   return {N, m};
 }
 
+// ---- the clusters as an index (csrc/ivf.hip) ------------------------------------------------
+void partition(const Tensor& labels, int64_t K, const Tensor& order, const Tensor& offsets, const Tensor& cells,
+               const c10::optional<Tensor>& rpos) {
+  TORCH_CHECK(labels.dim() == 1, "mikmeans: labels must be [n]");
+  const int64_t n = labels.size(0);
+  check_i32(labels, "labels", n);
+  TORCH_CHECK(K >= 1 && K <= mk::PARTITION_MAX_K, "mikmeans: partition takes 1 <= K <= ", mk::PARTITION_MAX_K,
+              ", got ", K);
+  TORCH_CHECK(n < (int64_t(1) << 32), "mikmeans: partition takes fewer than 2^32 rows");
+  check_i64(order, "order", n);
+  check_i64(offsets, "offsets", K + 1);
+  check_i64(cells, "cells", K * mk::partition_blocks(n, (int)K));
+  if (rpos.has_value() && rpos->defined()) check_i64(*rpos, "rpos", n);
+  const int dev = labels.get_device();
+  TORCH_CHECK(order.get_device() == dev && offsets.get_device() == dev && cells.get_device() == dev,
+              "mikmeans: partition tensors must share a device");
+  hip_check(mk::launch_partition(labels.data_ptr<int32_t>(), n, (int)K, order.data_ptr<int64_t>(),
+                                 offsets.data_ptr<int64_t>(), cells.data_ptr<int64_t>(), opt_ptr<int64_t>(rpos),
+                                 stream()),
+            "partition");
+}
+
+void ivf_pack(const Tensor& X, int64_t row0, const Tensor& labels, const Tensor& rpos, const Tensor& offsets,
+              const Tensor& toff, const Tensor& pack, const Tensor& cn, int64_t dpad) {
+  const int dt = dtype_of(X);
+  const int64_t ldx = check_points(X, dt);
+  const int64_t nb = X.size(0), n = labels.numel(), K = offsets.numel() - 1;
+  TORCH_CHECK(X.size(1) <= dpad && dpad % (4 * vec_of(dt)) == 0, "mikmeans: D exceeds dpad");
+  TORCH_CHECK(row0 >= 0 && row0 + nb <= n, "mikmeans: ivf_pack block outside the index's rows");
+  TORCH_CHECK(K >= 1, "mikmeans: offsets must be [K + 1]");
+  check_i32(labels, "labels", n);
+  check_i64(rpos, "rpos", n);
+  check_i64(offsets, "offsets", K + 1);
+  check_i64(toff, "toff", K + 1);
+  check_cuda(pack, "pack");
+  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == X.scalar_type() && pack.numel() % (16 * dpad) == 0,
+              "mikmeans: pack must be the points' dtype, whole 16-row tiles of dpad columns");
+  // every list padded to whole tiles takes at most (n + 15 K) / 16 tiles
+  TORCH_CHECK(pack.numel() / (16 * dpad) >= (n + 15 * K) / 16, "mikmeans: pack too small");
+  check_f32(cn, "cn", pack.numel() / dpad);
+  mk::IvfPackArgs a;
+  a.X = X.data_ptr(); a.nb = nb; a.D = (int)X.size(1); a.ldx = ldx; a.row0 = row0;
+  a.labels = labels.data_ptr<int32_t>(); a.rpos = rpos.data_ptr<int64_t>();
+  a.offsets = offsets.data_ptr<int64_t>(); a.toff = toff.data_ptr<int64_t>(); a.K = (int)K;
+  a.dtype = dt; a.dpad = (int)dpad; a.pack = pack.data_ptr(); a.cn = cn.data_ptr<float>();
+  hip_check(mk::launch_ivf_pack(a, stream()), "ivf_pack");
+}
+
+void ivf_scan(const Tensor& Q, const Tensor& qn, const Tensor& pack, const Tensor& cn, const Tensor& offsets,
+              const Tensor& toff, const Tensor& order, const Tensor& porder, const Tensor& poff, const Tensor& icum,
+              int64_t nprobe, int64_t dpad, int64_t P, int64_t max_items, const Tensor& out) {
+  const int dt = dtype_of(Q);
+  const int64_t ldq = check_points(Q, dt);
+  const int64_t nq = Q.size(0), K = offsets.numel() - 1, npairs = nq * nprobe;
+  TORCH_CHECK(Q.size(1) <= dpad, "mikmeans: D exceeds dpad");
+  TORCH_CHECK(K >= 1 && nprobe >= 1 && nprobe <= K, "mikmeans: ivf_scan needs 1 <= nprobe <= K");
+  check_f32(qn, "qn", nq);
+  check_cuda(pack, "pack");
+  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == Q.scalar_type() && pack.numel() % (16 * dpad) == 0,
+              "mikmeans: pack must be the queries' dtype, whole 16-row tiles of dpad columns");
+  check_f32(cn, "cn", pack.numel() / dpad);
+  check_i64(offsets, "offsets", K + 1);
+  check_i64(toff, "toff", K + 1);
+  check_i64(order, "order", 0);
+  check_i64(porder, "porder", npairs);
+  check_i64(poff, "poff", K + 1);
+  check_i64(icum, "icum", K + 1);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == npairs, "mikmeans: out must be [nq * nprobe, m]");
+  const int64_t m = out.size(1);
+  TORCH_CHECK(m >= 1 && m <= mk::TOPK_MAX, "mikmeans: ivf_scan needs 1 <= m <= ", mk::TOPK_MAX, ", got m = ", m);
+  check_i64(out, "out", npairs * m);
+  TORCH_CHECK(P == mk::ivf_scan_blocks(dt, (int)dpad, (int)m, npairs) || P == 1, "mikmeans: bad ivf_scan P ", P);
+  TORCH_CHECK(max_items >= npairs / (16 * P) && max_items <= npairs / (16 * P) + K + 1,
+              "mikmeans: bad ivf_scan max_items ", max_items);
+  mk::IvfScanArgs a;
+  a.Q = Q.data_ptr(); a.D = (int)Q.size(1); a.ldq = ldq; a.qn = qn.data_ptr<float>();
+  a.pack = pack.data_ptr(); a.cn = cn.data_ptr<float>();
+  a.offsets = offsets.data_ptr<int64_t>(); a.toff = toff.data_ptr<int64_t>(); a.order = order.data_ptr<int64_t>();
+  a.porder = porder.data_ptr<int64_t>(); a.poff = poff.data_ptr<int64_t>(); a.icum = icum.data_ptr<int64_t>();
+  a.K = (int)K; a.nprobe = (int)nprobe; a.m = (int)m; a.npairs = npairs; a.max_items = max_items;
+  a.out = reinterpret_cast<long long*>(out.data_ptr<int64_t>());
+  hip_check(mk::launch_ivf_scan(dt, (int)dpad, (int)P, a, stream()), "ivf_scan");
+}
+
 void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {
   TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUALITY_WORDS, "mikmeans: table must be [K, ",
               mk::QUALITY_WORDS, "]");
@@ -942,6 +1026,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topk", &topk, "the m nearest centres of every row (squared distances, ascending) on the MFMA tiles",
         py::arg("X"), py::arg("pack"), py::arg("cn"), py::arg("K"), py::arg("Kpad"), py::arg("dpad"), py::arg("xn"),
         py::arg("dist"), py::arg("idx"));
+  m.def("partition", &partition,
+        "stable partition of the rows by label: order (label after label, ascending within) and offsets",
+        py::arg("labels"), py::arg("K"), py::arg("order"), py::arg("offsets"), py::arg("cells"),
+        py::arg("rpos") = py::none());
+  m.def("partition_blocks", &mk::partition_blocks);
+  m.attr("PARTITION_MAX_K") = mk::PARTITION_MAX_K;
+  m.def("ivf_pack", &ivf_pack, "a block of the index's rows into the fragment-packed row pack, list after list",
+        py::arg("X"), py::arg("row0"), py::arg("labels"), py::arg("rpos"), py::arg("offsets"), py::arg("toff"),
+        py::arg("pack"), py::arg("cn"), py::arg("dpad"));
+  m.def("ivf_scan", &ivf_scan, "the m nearest rows of every (query, probed list) pair as (d2 bits << 32 | row) keys",
+        py::arg("Q"), py::arg("qn"), py::arg("pack"), py::arg("cn"), py::arg("offsets"), py::arg("toff"),
+        py::arg("order"), py::arg("porder"), py::arg("poff"), py::arg("icum"), py::arg("nprobe"), py::arg("dpad"),
+        py::arg("P"), py::arg("max_items"), py::arg("out"));
+  m.def("ivf_scan_blocks", &mk::ivf_scan_blocks);
+  m.attr("IVF_EMPTY_KEY") = (int64_t)mk::IVF_EMPTY_KEY;
   m.def("quality_accumulate", &quality_accumulate,
         "add the top-2 output's per-cluster quality words into table [K, QUALITY_WORDS] (integer atomics)",
         py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("path") = -1);

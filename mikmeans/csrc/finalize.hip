@@ -9,20 +9,9 @@
 // kernel streams (layout in kernels.h).  One workgroup per 32-centroid tile.
 #include "common.h"
 #include "kernels.h"
+#include "pack.h"   // store_pack, pack_elem (shared with the index's row pack, csrc/ivf.hip)
 
 namespace mk {
-
-// Packed layout (kernels.h): 16-centroid tiles; piece q of lane r+16g holds features
-// [(4q+g)V, (4q+g+1)V).
-template <typename T>
-__device__ __forceinline__ void store_pack(void* pack, int dpad, int k, int d, float v) {
-  constexpr int V = Elem<T>::V;
-  const int nq = dpad / (4 * V);
-  const int t = k >> 4, r = k & 15;
-  const int g = (d / V) & 3, q = d / (4 * V);
-  const int64_t off = ((int64_t)(t * nq + q) * 64 + r + 16 * g) * V + d % V;
-  ((T*)pack)[off] = Elem<T>::from_f32(v);
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
@@ -60,11 +49,9 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
       const float diff = nv - old;
       shift += diff * diff;
       const float q = (a.dtype == DT_BF16) ? round_bf16(nv) : nv;
-      cn += q * q;
+      pack_elem(a.dtype, a.pack, a.dpad, k, d, q, cn);
       const float dq = q - ((a.dtype == DT_BF16) ? round_bf16(old) : old);
       qs += dq * dq;
-      if (a.dtype == DT_BF16) store_pack<uint16_t>(a.pack, a.dpad, k, d, -2.f * q);
-      else store_pack<float>(a.pack, a.dpad, k, d, -2.f * q);
     }
     for (int d = a.D + part; d < a.dpad; d += 8) {
       if (a.dtype == DT_BF16) store_pack<uint16_t>(a.pack, a.dpad, k, d, 0.f);

@@ -1,0 +1,371 @@
+// mikmeans — the fitted clusters as an inverted-file index (build_index / search), for gfx950.
+//
+// Three pieces, each in launches of its own; no workgroup ever waits for another.
+//
+// 1. Stable partition by label: order = the rows with a label in [0, K), label after label and
+//    ascending inside a label, offsets = where each label's rows start (the stable sort of the
+//    labels and the cumulative bincount).  Count, scan, scatter in the style of the compaction
+//    kernels of csrc/rows.hip: a workgroup counts its contiguous rows per label in LDS, one
+//    workgroup scans the [K][blocks] counts (label-major, so a label's blocks follow each other),
+//    and the scatter pass recounts per wave, turns the [4 waves][K] counters into running
+//    positions (block base + the waves before) and walks its rows again: the lanes of a wave that
+//    share a label are found by ballots, a lane's rank among them is the mbcnt of that ballot and
+//    the group's first lane moves the label's position on.  LDS atomics only count; no position
+//    depends on an atomic's return order, so order is the same on every launch.  The same op
+//    groups the (query, probe) pairs of a search by list.
+// 2. Row pack: the indexed rows, list after list and each list padded to whole 16-row tiles, in
+//    the fragment-packed layout of kernels.h with their cn -- bit for bit what the centre pack
+//    (csrc/finalize.hip, pack-only) makes of the same rows: both run pack_elem (pack.h) over the
+//    same features per lane and sum the eight lanes by the same butterfly.  X is read in its own
+//    dtype.
+// 3. Scan: a wave's work item is (list, block of up to 16 P pairs probing it), the items ordered by
+//    list so that neighbouring waves walk the same tiles.  The wave finds its item by a binary
+//    search of the per-list item counts' cumulative sum (the grid is launched at its upper bound,
+//    waves past the total exit), gathers its queries' fragments as topk_kernel holds rows, walks
+//    the list's tiles straight from global memory and keeps the M best (d2 bits, position in
+//    list) per lane with the insertion of topk.h; a query's four lanes merge through LDS and lane
+//    r writes the pair's m keys (d2 bits << 32 | row).  d2 is bitwise the transform kernel's value
+//    for (query, row) with the rows packed as centres: the same cn seed, the same MFMA k-step
+//    order, max(xn_q + acc, 0).
+#include "pack.h"
+#include "topk.h"
+
+namespace mk {
+
+// ---- 1. stable partition -------------------------------------------------------------------
+constexpr int PT_T = 256;            // threads of a count / scatter workgroup (4 waves)
+constexpr int PT_MAX_BLOCKS = 1024;
+constexpr int64_t PT_MAX_CELLS = 1 << 20;   // K * blocks: what the one-workgroup scan walks
+
+int64_t partition_blocks(int64_t n, int K) {
+  int64_t cap = PT_MAX_CELLS / (K > 0 ? K : 1);
+  cap = cap < 1 ? 1 : (cap > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : cap);
+  const int64_t want = (n + 1023) / 1024;
+  return want < 1 ? 1 : (want < cap ? want : cap);
+}
+// rows of a workgroup: a multiple of 256, so every wave's quarter is whole 64-row steps
+static int64_t partition_block_rows(int64_t n, int64_t nb) { return ((n + nb - 1) / nb + 255) / 256 * 256; }
+
+__global__ __launch_bounds__(PT_T) void partition_count_kernel(const int32_t* __restrict__ labels, int64_t n, int K,
+                                                              int64_t block_rows, int64_t nb,
+                                                              int64_t* __restrict__ cells) {
+  extern __shared__ uint32_t pt_lds[];
+  for (int k = threadIdx.x; k < K; k += PT_T) pt_lds[k] = 0u;
+  __syncthreads();
+  const int64_t r0 = (int64_t)blockIdx.x * block_rows;
+  const int64_t r1 = r0 + block_rows < n ? r0 + block_rows : n;
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += PT_T) {
+    const int l = labels[i];
+    if ((unsigned)l < (unsigned)K) atomicAdd(&pt_lds[l], 1u);
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < K; k += PT_T) cells[(int64_t)k * nb + blockIdx.x] = pt_lds[k];
+}
+
+// cells (label-major counts) -> their exclusive prefix sums, in place; offsets[k] = the prefix at
+// label k's first block, offsets[K] = the total.  One workgroup, fixed order.
+__global__ __launch_bounds__(1024) void partition_scan_kernel(int64_t* __restrict__ cells, int64_t nb, int K,
+                                                              int64_t* __restrict__ offsets) {
+  __shared__ int64_t wsum[16];
+  __shared__ int64_t tot;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t total = (int64_t)K * nb;
+  int64_t carry = 0;
+  for (int64_t s0 = 0; s0 < total; s0 += 1024) {
+    const int64_t i = s0 + threadIdx.x;
+    const int64_t v = i < total ? cells[i] : 0;
+    int64_t incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int64_t u = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += u;
+    }
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    for (int j = 0; j < w; ++j) incl += wsum[j];
+    if (threadIdx.x == 1023) tot = incl;
+    if (i < total) {
+      const int64_t excl = carry + incl - v;
+      cells[i] = excl;
+      if (i % nb == 0) offsets[i / nb] = excl;
+    }
+    __syncthreads();
+    carry += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) offsets[K] = carry;
+}
+
+__global__ __launch_bounds__(PT_T) void partition_scatter_kernel(const int32_t* __restrict__ labels, int64_t n, int K,
+                                                                int64_t block_rows, int64_t nb,
+                                                                const int64_t* __restrict__ cells,
+                                                                int64_t* __restrict__ order,
+                                                                int64_t* __restrict__ rpos) {
+  extern __shared__ uint32_t pt_lds[];   // [4 waves][K]: counts, then running positions
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int k = threadIdx.x; k < 4 * K; k += PT_T) pt_lds[k] = 0u;
+  __syncthreads();
+  const int64_t q = block_rows / 4;
+  const int64_t r0 = (int64_t)blockIdx.x * block_rows + w * q;
+  const int64_t r1 = r0 + q < n ? r0 + q : n;
+  uint32_t* mine = pt_lds + (int64_t)w * K;
+  for (int64_t base = r0; base < r1; base += 64) {
+    const int64_t i = base + lane;
+    const int l = i < r1 ? labels[i] : -1;
+    if ((unsigned)l < (unsigned)K) atomicAdd(&mine[l], 1u);
+  }
+  __syncthreads();
+  // a wave's first position of label k: the block's base, then the waves before it (fixed order)
+  for (int k = threadIdx.x; k < K; k += PT_T) {
+    uint32_t p = (uint32_t)cells[(int64_t)k * nb + blockIdx.x];   // (fewer than 2^32 rows)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t c = pt_lds[j * K + k];
+      pt_lds[j * K + k] = p;
+      p += c;
+    }
+  }
+  __syncthreads();
+  for (int64_t base = r0; base < r1; base += 64) {
+    const int64_t i = base + lane;
+    const int l = i < r1 ? labels[i] : -1;
+    bool pend = (unsigned)l < (unsigned)K;
+    unsigned long long pm;
+    while ((pm = __builtin_amdgcn_ballot_w64(pend)) != 0ull) {
+      const int lead = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(pm));
+      const int lk = __builtin_amdgcn_readlane(l, lead);
+      const bool hit = pend && l == lk;
+      const unsigned long long mm = __builtin_amdgcn_ballot_w64(hit);
+      const uint32_t start = mine[lk];
+      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mm, 0u));
+      if (hit) {
+        order[start + rank] = i;
+        if (rpos) rpos[i] = (int64_t)(start + rank);
+      }
+      if (lane == lead) mine[lk] = start + (uint32_t)__builtin_popcountll(mm);
+      pend = pend && !hit;
+    }
+  }
+}
+
+hipError_t launch_partition(const int32_t* labels, int64_t n, int K, int64_t* order, int64_t* offsets, int64_t* cells,
+                            int64_t* rpos, hipStream_t s) {
+  if (K < 1 || K > PARTITION_MAX_K || n < 0 || n >= ((int64_t)1 << 32)) return hipErrorInvalidValue;
+  const int64_t nb = partition_blocks(n, K), br = partition_block_rows(n, nb);
+  hipError_t e = hipSuccess;
+  if (n > 0) {
+    e = hipMemsetAsync(order, 0xff, (size_t)n * 8, s);   // the tail past the valid rows: -1
+    if (e == hipSuccess && rpos) e = hipMemsetAsync(rpos, 0xff, (size_t)n * 8, s);
+    if (e != hipSuccess) return e;
+  }
+  fold_lds_optin<partition_scatter_kernel>();
+  hipLaunchKernelGGL(partition_count_kernel, dim3((unsigned)nb), dim3(PT_T), (size_t)K * 4, s, labels, n, K, br, nb,
+                     cells);
+  hipLaunchKernelGGL(partition_scan_kernel, dim3(1), dim3(1024), 0, s, cells, nb, K, offsets);
+  if (n > 0)
+    hipLaunchKernelGGL(partition_scatter_kernel, dim3((unsigned)nb), dim3(PT_T), (size_t)K * 16, s, labels, n, K, br,
+                       nb, cells, order, rpos);
+  return hipGetLastError();
+}
+
+// ---- 2. row pack ---------------------------------------------------------------------------
+// Eight lanes a row, 32 rows a workgroup, as finalize_kernel packs centres.  Row i of the block
+// (row row0 + i of the index) goes to packed row 16 toff[k] + (its position - offsets[k]), k its
+// list; rows in no list (rpos < 0) are skipped.  Pad rows and pad columns keep what the caller
+// filled the buffers with (zeros, and PAD_SCORE in cn).
+template <typename T>
+__global__ __launch_bounds__(256) void ivf_pack_kernel(IvfPackArgs a) {
+  const int kk = threadIdx.x >> 3, part = threadIdx.x & 7;
+  const int64_t i = (int64_t)blockIdx.x * 32 + kk;
+  float cn = 0.f;
+  int64_t dst = -1;
+  if (i < a.nb) {
+    const int64_t row = a.row0 + i;
+    const int64_t p = a.rpos[row];
+    if (p >= 0) {
+      const int k = a.labels[row];
+      dst = a.toff[k] * 16 + (p - a.offsets[k]);
+      const T* x = (const T*)a.X + i * a.ldx;
+      for (int d = part; d < a.D; d += 8) {
+        const float old = Elem<T>::to_f32(x[d]);
+        const float q = (a.dtype == DT_BF16) ? round_bf16(old) : old;
+        pack_elem(a.dtype, a.pack, a.dpad, dst, d, q, cn);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) cn += __shfl_xor(cn, o, 64);
+  if (part == 0 && dst >= 0) a.cn[dst] = cn;
+}
+
+hipError_t launch_ivf_pack(const IvfPackArgs& a, hipStream_t s) {
+  if (a.nb <= 0) return hipSuccess;
+  if (a.D > a.dpad || a.K < 1) return hipErrorInvalidValue;
+  const unsigned nb = (unsigned)((a.nb + 31) / 32);
+  if (a.dtype == DT_BF16) hipLaunchKernelGGL(ivf_pack_kernel<uint16_t>, dim3(nb), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(ivf_pack_kernel<float>, dim3(nb), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---- 3. scan ---------------------------------------------------------------------------------
+template <typename T, int DPAD, int P, int M>
+__global__ __launch_bounds__(TK_NW * 64, 2) void ivf_scan_kernel(IvfScanArgs a) {
+  constexpr int V = Elem<T>::V;
+  constexpr int NQ = DPAD / 4 / V;
+  constexpr bool XREG = topk_xreg(NQ, M);
+  __shared__ unsigned long long sm[TK_NW * M * 64];
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int64_t item = (int64_t)blockIdx.x * TK_NW + wid;
+  if (item >= a.icum[a.K]) return;   // (wave-uniform; the kernel has no workgroup barrier)
+  int lo = 0, hi = a.K;              // the list l with icum[l] <= item < icum[l + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.icum[mid] <= item) lo = mid;
+    else hi = mid;
+  }
+  const int l = lo;
+  const int64_t p0 = a.poff[l] + (item - a.icum[l]) * (P * 16);
+  const int64_t pleft = a.poff[l + 1] - p0;
+  const int np = (int)(pleft < P * 16 ? pleft : P * 16);   // the item's pairs, >= 1
+  const int64_t o0 = a.offsets[l];
+  const int nl = (int)(a.offsets[l + 1] - o0);             // the list's rows
+  u32x4 xr[P][XREG ? NQ : 1];
+  const T* xp[P];
+  float xn[P];
+  int64_t pid[P];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    const int slot = p * 16 + r;
+    pid[p] = a.porder[p0 + (slot < np ? slot : np - 1)];
+    const int64_t row = pid[p] / a.nprobe;
+    xp[p] = (const T*)a.Q + row * a.ldq + g * V;
+    if constexpr (XREG) {
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) xr[p][q] = load_piece<V>(xp[p], q, g, a.D);
+    }
+    xn[p] = a.qn[row];
+  }
+  uint32_t bv[P][M];
+  int bi[P][M];
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      bv[p][j] = TK_EMPTY;
+      bi[p][j] = TK_NOIDX;
+    }
+  }
+  const int64_t t0 = a.toff[l];
+  const T* pack = (const T*)a.pack + t0 * (NQ * 64 * V);
+  const float* cnl = a.cn + t0 * 16;
+  const int ntile = (nl + 15) / 16;
+  for (int t = 0; t < ntile; ++t) {
+    const f32x4 ci = *(const f32x4*)(cnl + t * 16 + 4 * g);
+    f32x4 acc[P];
+#pragma unroll
+    for (int p = 0; p < P; ++p) acc[p] = ci;
+    const T* tp = pack + ((int64_t)t * NQ * 64 + lane) * V;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+      const u32x4 aq = *(const u32x4*)(tp + (int64_t)q * 64 * V);
+#pragma unroll
+      for (int p = 0; p < P; ++p)
+        acc[p] = KMfma<T>::run(aq, XREG ? xr[p][q] : load_piece<V>(xp[p], q, g, a.D), acc[p]);
+    }
+    const int k0 = t * 16 + 4 * g;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d2 = fmaxf(xn[p] + acc[p][e], 0.f);
+        // a position past the list's length is an empty candidate: the strict compare never takes it
+        const uint32_t c = k0 + e < nl ? __float_as_uint(d2) : TK_EMPTY;
+        const int ck = k0 + e;
+        if (__builtin_amdgcn_ballot_w64(c < bv[p][M - 1]) == 0) continue;
+        tk_insert<M>(bv[p], bi[p], c, ck);
+      }
+    }
+  }
+  MK_LDS unsigned long long* ws = (MK_LDS unsigned long long*)sm + wid * (M * 64);
+  const int64_t* ord = a.order + o0;
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    tk_stage<M>(ws, lane, bv[p], bi[p]);
+    if (g == 0 && p * 16 + r < np) {
+      long long* out = a.out + pid[p] * a.m;
+      tk_merge4<M>(ws, r, a.m, [&](int j, unsigned long long best) {
+        const uint32_t bits = (uint32_t)(best >> 32);
+        // an empty slot: the largest int64, behind every key in the per-query sort
+        out[j] = bits == TK_EMPTY
+                     ? (long long)IVF_EMPTY_KEY
+                     : (long long)(((unsigned long long)bits << 32) | (uint32_t)ord[(uint32_t)best]);
+      });
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // the next block's keys overwrite the slab
+  }
+}
+
+template <typename T, int DPAD, int P, int M>
+static hipError_t launch_is_p(const IvfScanArgs& a, hipStream_t s) {
+  const int64_t nb = (a.max_items + TK_NW - 1) / TK_NW;
+  hipLaunchKernelGGL((ivf_scan_kernel<T, DPAD, P, M>), dim3((unsigned)nb), dim3(TK_NW * 64), 0, s, a);
+  return hipGetLastError();
+}
+
+template <typename T, int DPAD, int M>
+static hipError_t launch_is_m(int P, const IvfScanArgs& a, hipStream_t s) {
+  constexpr int PF = topk_blocks(DPAD / 4 / Elem<T>::V, M);
+  if (P == 1) return launch_is_p<T, DPAD, 1, M>(a, s);
+  if (P == PF) return launch_is_p<T, DPAD, PF, M>(a, s);
+  return hipErrorInvalidValue;
+}
+
+template <typename T, int DPAD>
+static hipError_t launch_is(int P, const IvfScanArgs& a, hipStream_t s) {
+  return a.m <= 8 ? launch_is_m<T, DPAD, 8>(P, a, s) : launch_is_m<T, DPAD, 32>(P, a, s);
+}
+
+// Pair blocks per wave: topk's rule (topk_blocks; one block for a small batch of pairs, so more
+// waves share the work)
+int ivf_scan_blocks(int dtype, int dpad, int m, int64_t npairs) {
+  const int nq = dpad / 4 / (dtype == DT_BF16 ? 8 : 4);
+  const int P = topk_blocks(nq, m <= 8 ? 8 : 32);
+  return (P > 1 && npairs < (int64_t)32768 * P) ? 1 : P;
+}
+
+hipError_t launch_ivf_scan(int dtype, int dpad, int P, const IvfScanArgs& a, hipStream_t s) {
+  if (a.npairs <= 0 || a.max_items <= 0) return hipSuccess;
+  if (a.K < 1 || a.m < 1 || a.m > TOPK_MAX || a.nprobe < 1 || a.D > dpad) return hipErrorInvalidValue;
+  if ((a.max_items + TK_NW - 1) / TK_NW > 0x7fffffff) return hipErrorInvalidValue;
+  if (dtype == DT_BF16) {
+    switch (dpad) {
+      case 32: return launch_is<uint16_t, 32>(P, a, s);
+      case 64: return launch_is<uint16_t, 64>(P, a, s);
+      case 128: return launch_is<uint16_t, 128>(P, a, s);
+      case 256: return launch_is<uint16_t, 256>(P, a, s);
+      case 384: return launch_is<uint16_t, 384>(P, a, s);
+      case 512: return launch_is<uint16_t, 512>(P, a, s);
+      case 768: return launch_is<uint16_t, 768>(P, a, s);
+      case 1024: return launch_is<uint16_t, 1024>(P, a, s);
+    }
+  } else {
+    switch (dpad) {
+      case 16: return launch_is<float, 16>(P, a, s);
+      case 32: return launch_is<float, 32>(P, a, s);
+      case 64: return launch_is<float, 64>(P, a, s);
+      case 128: return launch_is<float, 128>(P, a, s);
+      case 256: return launch_is<float, 256>(P, a, s);
+      case 384: return launch_is<float, 384>(P, a, s);
+      case 512: return launch_is<float, 512>(P, a, s);
+      case 768: return launch_is<float, 768>(P, a, s);
+      case 1024: return launch_is<float, 1024>(P, a, s);
+    }
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace mk

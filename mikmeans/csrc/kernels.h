@@ -122,6 +122,59 @@ struct TopkArgs {
 };
 hipError_t launch_topk(int dtype, int dpad, const TopkArgs& a, hipStream_t s);
 
+// ---- the clusters as an inverted-file index (csrc/ivf.hip) --------------------------------
+// Stable partition by label: order[0..offsets[K]) = the rows i with labels[i] in [0, K), label
+// after label and ascending within a label, the tail of order [n] -1; offsets [K + 1] = where each
+// label's rows start (the cumulative bincount).  rpos (optional, [n]): every row's position in
+// order, -1 for a row in no list.  cells: int64 scratch [K * partition_blocks(n, K)].  Bitwise
+// the same on every launch; no host read.  K <= PARTITION_MAX_K (the scatter pass keeps
+// [4 waves][K] u32 counters in FOLD_LDS_BYTES of LDS) and n < 2^32.
+constexpr int PARTITION_MAX_K = FOLD_LDS_BYTES / 16;   // 10240
+int64_t partition_blocks(int64_t n, int K);
+hipError_t launch_partition(const int32_t* labels, int64_t n, int K, int64_t* order, int64_t* offsets, int64_t* cells,
+                            int64_t* rpos, hipStream_t s);
+// Row pack: rows [row0, row0 + nb) of the index (X: the block's rows, in their own dtype) into
+// the fragment-packed layout above, list after list, list k from tile toff[k] on (each list
+// padded to whole 16-row tiles): row i lands at packed row 16 toff[k] + rpos[i] - offsets[k],
+// k = labels[i]; rows with rpos < 0 are skipped.  pack / cn must be filled with zeros /
+// PAD_SCORE before the first block.  A list's segment is bitwise launch_finalize's pack-only
+// output for its rows.
+struct IvfPackArgs {
+  const void* X; int64_t nb; int D; int64_t ldx;
+  int64_t row0;
+  const int32_t* labels;     // [n] every row's list
+  const int64_t* rpos;       // [n] launch_partition's
+  const int64_t* offsets;    // [K + 1]
+  const int64_t* toff;       // [K + 1] first tile of each list
+  int K;
+  int dtype; int dpad; void* pack; float* cn;
+};
+hipError_t launch_ivf_pack(const IvfPackArgs& a, hipStream_t s);
+// Scan: for every (query, probe) pair -- pair id = query * nprobe + probe, grouped by probed list
+// (porder / poff: launch_partition of the pairs' lists) -- the m smallest keys
+// (d2 bits << 32 | row) over the rows of the pair's list, ascending, into out[pair id][0..m);
+// IVF_EMPTY_KEY where the list has fewer than m rows.  d2 is bitwise launch_transform's value of
+// the query against the row packed as a centre.  A wave takes (list, block of up to 16 P pairs):
+// icum [K + 1] = the cumulative sum of ceil(pairs_l / 16 P), max_items an upper bound of icum[K]
+// (the grid; waves past icum[K] exit).  P from ivf_scan_blocks.  1 <= m <= TOPK_MAX.
+constexpr long long IVF_EMPTY_KEY = 0x7fffffffffffffffLL;
+struct IvfScanArgs {
+  const void* Q; int D; int64_t ldq;
+  const float* qn;           // |q|^2 per query
+  const void* pack; const float* cn;   // the row pack
+  const int64_t* offsets;    // [K + 1] list starts in order
+  const int64_t* toff;       // [K + 1] list starts in tiles
+  const int64_t* order;      // row ids, list after list
+  const int64_t* porder;     // [npairs] pair ids grouped by list
+  const int64_t* poff;       // [K + 1]
+  const int64_t* icum;       // [K + 1]
+  int K; int nprobe; int m;
+  int64_t npairs; int64_t max_items;
+  long long* out;            // [npairs, m]
+};
+int ivf_scan_blocks(int dtype, int dpad, int m, int64_t npairs);
+hipError_t launch_ivf_scan(int dtype, int dpad, int P, const IvfScanArgs& a, hipStream_t s);
+
 // ---- per-cluster quality table (csrc/quality.hip) ----------------------------------------
 // Folds launch_topk's output (m = 1 or 2) into table[K][QUALITY_WORDS] (u64, only ever added
 // into) with integer atomics: per label the digits of sum a^2 and the row count, the digits of

@@ -1,0 +1,113 @@
+// mikmeans — the pieces the register-list kernels share (csrc/topk.hip: the m nearest centres of
+// every row; csrc/ivf.hip: the m nearest indexed rows of every (query, probed list) pair): the
+// MFMA k-step, the row-piece load, the per-lane sorted list's insertion and the merge of a row's
+// four lane lists through LDS.
+#pragma once
+#include "common.h"
+#include "kernels.h"
+
+namespace mk {
+
+template <typename T> struct KMfma;
+template <> struct KMfma<uint16_t> {
+  __device__ static __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, const f32x4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(short8, a), __builtin_bit_cast(short8, b), c,
+                                                   0, 0, 0);
+  }
+};
+template <> struct KMfma<float> {
+  __device__ static __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, f32x4 c) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
+    return c;
+  }
+};
+
+constexpr int TK_NW = 4;                    // waves per workgroup
+constexpr uint32_t TK_EMPTY = 0xffffffffu;  // list slot without a candidate (above every d2 >= 0)
+constexpr int TK_NOIDX = 0x7fffffff;
+
+// Piece q of a row for lane group g (features [(4q + g)V, +V)); zero past the row's D columns
+template <int V, typename T>
+__device__ __forceinline__ u32x4 load_piece(const T* rp, int q, int g, int D) {
+  return (4 * q + g) * V < D ? *(const u32x4*)(rp + 4 * q * V) : u32x4{0u, 0u, 0u, 0u};
+}
+
+// Whether a wave's rows stay in registers (4 NQ VGPRs a block) beside the list: the kernel is
+// held to the 256 VGPRs of two waves per SIMD, and the M = 32 insertion needs ~140 of them
+// (NQ = 32 spilled 20), the M = 8 one ~50.  Past that (f32 D > 768; the long list from bf16
+// D > 768 and f32 D > 384) the row fragments are fetched again for every tile (L1 / L2 hits).
+constexpr bool topk_xreg(int nq, int m) { return nq <= (m > 8 ? 24 : 48); }
+
+// Row blocks per wave: the rows' fragments (4 NQ VGPRs), the list (2 M) and the accumulators
+// (4) of every block within ~176 VGPRs, at most 4 blocks -- two waves per SIMD wherever the
+// transform kernel has them (tests/test_gpu_topk.py reads the built code object).
+constexpr int topk_blocks(int nq, int m) {
+  const int p = 176 / (4 * nq + 2 * m + 4);
+  return p < 1 ? 1 : (p > 4 ? 4 : p);
+}
+
+// Candidate (c, ck) into a lane's sorted list (the caller has skipped it where no lane of the
+// wave has c < bv[M - 1]): slot j takes its left neighbour where c goes in front of both, c
+// itself where it goes in front of slot j only (every compare against c: a displaced entry
+// never passes an equal one, which a compare-and-swap chain of the carried entry would do)
+template <int M>
+__device__ __forceinline__ void tk_insert(uint32_t (&bv)[M], int (&bi)[M], uint32_t c, int ck) {
+#pragma unroll
+  for (int j = M - 1; j > 0; --j) {
+    const bool s = c < bv[j], sl = c < bv[j - 1];
+    bv[j] = s ? (sl ? bv[j - 1] : c) : bv[j];
+    bi[j] = s ? (sl ? bi[j - 1] : ck) : bi[j];
+  }
+  const bool s0 = c < bv[0];
+  bv[0] = s0 ? c : bv[0];
+  bi[0] = s0 ? ck : bi[0];
+}
+
+// A row block's lists to the wave's LDS slab as (bits << 32 | index) keys, [slot][lane]
+// (conflict-free), fenced for the merging lanes
+template <int M>
+__device__ __forceinline__ void tk_stage(MK_LDS unsigned long long* ws, int lane, const uint32_t (&bv)[M],
+                                         const int (&bi)[M]) {
+#pragma unroll
+  for (int j = 0; j < M; ++j) ws[j * 64 + lane] = ((unsigned long long)bv[j] << 32) | (uint32_t)bi[j];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Lane r merges the four lists of its row (lanes r, r + 16, r + 32, r + 48) in a rolled loop:
+// emit(j, key) for the m smallest keys in ascending order
+template <int M, typename Emit>
+__device__ __forceinline__ void tk_merge4(const MK_LDS unsigned long long* ws, int r, int m, Emit emit) {
+  unsigned long long hk[4];
+  int hp[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    hp[q] = 0;
+    hk[q] = ws[r + 16 * q];
+  }
+#pragma unroll 1
+  for (int j = 0; j < m; ++j) {
+    unsigned long long best = hk[0];
+    int sel = 0;
+#pragma unroll
+    for (int q = 1; q < 4; ++q) {
+      if (hk[q] < best) {
+        best = hk[q];
+        sel = q;
+      }
+    }
+    emit(j, best);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (sel == q) {
+        ++hp[q];
+        hk[q] = hp[q] < M ? ws[hp[q] * 64 + r + 16 * q] : ~0ull;
+      }
+    }
+  }
+}
+
+}  // namespace mk

@@ -18,42 +18,9 @@
 // r + 32, r + 48) go through LDS as (d2 bits << 32 | k) keys and lane r merges them in a
 // rolled loop -- once per wave and row block, so its speed matters little -- writing the
 // row's first m winners.
-#include "common.h"
-#include "kernels.h"
+#include "topk.h"   // the MFMA step, the list insertion and the merge (shared with csrc/ivf.hip)
 
 namespace mk {
-
-template <typename T> struct KMfma;
-template <> struct KMfma<uint16_t> {
-  __device__ static __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(short8, a), __builtin_bit_cast(short8, b), c,
-                                                   0, 0, 0);
-  }
-};
-template <> struct KMfma<float> {
-  __device__ static __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, f32x4 c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
-    return c;
-  }
-};
-
-constexpr int TK_NW = 4;                    // waves per workgroup
-constexpr uint32_t TK_EMPTY = 0xffffffffu;  // list slot without a candidate (above every d2 >= 0)
-constexpr int TK_NOIDX = 0x7fffffff;
-
-// Piece q of a row for lane group g (features [(4q + g)V, +V)); zero past the row's D columns
-template <int V, typename T>
-__device__ __forceinline__ u32x4 load_piece(const T* rp, int q, int g, int D) {
-  return (4 * q + g) * V < D ? *(const u32x4*)(rp + 4 * q * V) : u32x4{0u, 0u, 0u, 0u};
-}
-
-// Whether a wave's rows stay in registers (4 NQ VGPRs a block) beside the list: the kernel is
-// held to the 256 VGPRs of two waves per SIMD, and the M = 32 insertion needs ~140 of them
-// (NQ = 32 spilled 20), the M = 8 one ~50.  Past that (f32 D > 768; the long list from bf16
-// D > 768 and f32 D > 384) the row fragments are fetched again for every tile (L1 / L2 hits).
-constexpr bool topk_xreg(int nq, int m) { return nq <= (m > 8 ? 24 : 48); }
 
 template <typename T, int DPAD, int P, int M>
 __global__ __launch_bounds__(TK_NW * 64, 2) void topk_kernel(TopkArgs a) {
@@ -115,18 +82,7 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void topk_kernel(TopkArgs a) {
         const uint32_t c = k0 + e < a.K ? __float_as_uint(d2) : TK_EMPTY;
         const int ck = k0 + e;
         if (__builtin_amdgcn_ballot_w64(c < bv[p][M - 1]) == 0) continue;
-        // slot j takes its left neighbour where c goes in front of both, c itself where it
-        // goes in front of slot j only (every compare against c: a displaced entry never
-        // passes an equal one, which a compare-and-swap chain of the carried entry would do)
-#pragma unroll
-        for (int j = M - 1; j > 0; --j) {
-          const bool s = c < bv[p][j], sl = c < bv[p][j - 1];
-          bv[p][j] = s ? (sl ? bv[p][j - 1] : c) : bv[p][j];
-          bi[p][j] = s ? (sl ? bi[p][j - 1] : ck) : bi[p][j];
-        }
-        const bool s0 = c < bv[p][0];
-        bv[p][0] = s0 ? c : bv[p][0];
-        bi[p][0] = s0 ? ck : bi[p][0];
+        tk_insert<M>(bv[p], bi[p], c, ck);
       }
     }
   }
@@ -134,55 +90,19 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void topk_kernel(TopkArgs a) {
   MK_LDS unsigned long long* ws = (MK_LDS unsigned long long*)sm + wid * (M * 64);
 #pragma unroll
   for (int p = 0; p < P; ++p) {
-#pragma unroll
-    for (int j = 0; j < M; ++j) ws[j * 64 + lane] = ((unsigned long long)bv[p][j] << 32) | (uint32_t)bi[p][j];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    tk_stage<M>(ws, lane, bv[p], bi[p]);
     const int64_t row = pbase + p * 16 + r;
     if (g == 0 && row < a.N) {
-      unsigned long long hk[4];
-      int hp[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        hp[q] = 0;
-        hk[q] = ws[r + 16 * q];
-      }
       float* od = a.dist + row * a.m;
       int32_t* oi = a.idx + row * a.m;
-#pragma unroll 1
-      for (int j = 0; j < a.m; ++j) {
-        unsigned long long best = hk[0];
-        int sel = 0;
-#pragma unroll
-        for (int q = 1; q < 4; ++q) {
-          if (hk[q] < best) {
-            best = hk[q];
-            sel = q;
-          }
-        }
+      tk_merge4<M>(ws, r, a.m, [&](int j, unsigned long long best) {
         od[j] = __uint_as_float((uint32_t)(best >> 32));
         oi[j] = (int32_t)(uint32_t)best;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (sel == q) {
-            ++hp[q];
-            hk[q] = hp[q] < M ? ws[hp[q] * 64 + r + 16 * q] : ~0ull;
-          }
-        }
-      }
+      });
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();   // the next block's keys overwrite the slab
   }
-}
-
-// Row blocks per wave: the rows' fragments (4 NQ VGPRs), the list (2 M) and the accumulators
-// (4) of every block within ~176 VGPRs, at most 4 blocks -- two waves per SIMD wherever the
-// transform kernel has them (tests/test_gpu_topk.py reads the built code object).
-constexpr int topk_blocks(int nq, int m) {
-  const int p = 176 / (4 * nq + 2 * m + 4);
-  return p < 1 ? 1 : (p > 4 ? 4 : p);
 }
 
 template <typename T, int DPAD, int P, int M>

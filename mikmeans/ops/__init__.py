@@ -491,3 +491,8 @@ from .analytics import *  # noqa: E402,F401,F403
 from .analytics import __all__ as _analytics_all  # noqa: E402
 
 __all__ += _analytics_all
+
+from .index import *  # noqa: E402,F401,F403
+from .index import __all__ as _index_all  # noqa: E402
+
+__all__ += _index_all

@@ -273,3 +273,72 @@ def cluster_sums(X: torch.Tensor, labels: torch.Tensor, K: int, weights=None):
         counts = torch.bincount(lab, minlength=K).to(torch.float64)
     sums = torch.zeros((K, X.shape[1]), dtype=torch.float64, device=X.device).index_add_(0, lab, Xd)
     return sums, counts
+
+
+PARTITION_MAX_K = 10240             # csrc/kernels.h PARTITION_MAX_K (the native partition's largest K)
+IVF_EMPTY_KEY = (1 << 63) - 1       # csrc/kernels.h IVF_EMPTY_KEY: a search slot without a row
+PAD_SCORE = 1.0e30                  # csrc/common.h PAD_SCORE: cn of a pad row
+
+
+def partition(labels: torch.Tensor, K: int):
+    """``(order, offsets, rpos)`` of a stable partition of the rows by label (csrc/ivf.hip in torch
+    arithmetic): ``order`` int64 [n] = the rows whose label lies in [0, K), label after label and
+    ascending within a label (a stable sort), tail -1; ``offsets`` int64 [K + 1] the cumulative
+    bincount; ``rpos`` int64 [n] every row's position in ``order``, -1 for a row in no list."""
+    lab = labels.to(torch.int64)
+    n, dev = lab.numel(), lab.device
+    rows = ((lab >= 0) & (lab < K)).nonzero().flatten()
+    kept = lab[rows]
+    perm = torch.sort(kept, stable=True).indices
+    order = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    order[: rows.numel()] = rows[perm]
+    offsets = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(torch.bincount(kept, minlength=K), 0)
+    rpos = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    rpos[rows[perm]] = torch.arange(rows.numel(), dtype=torch.int64, device=dev)
+    return order, offsets, rpos
+
+
+def index_pack(X: torch.Tensor, row0: int, labels: torch.Tensor, rpos: torch.Tensor, offsets: torch.Tensor,
+               toff: torch.Tensor, rows_out: torch.Tensor, cn: torch.Tensor) -> None:
+    """Rows [row0, row0 + nb) of an index into its natural-layout row store ``rows_out``
+    ([16 tiles, cols]) and ``cn`` (their squared norms): row i lands at
+    ``16 toff[k] + rpos[i] - offsets[k]``, k its list (csrc/ivf.hip's row pack without the
+    fragment layout)."""
+    nb = X.shape[0]
+    p = rpos[row0 : row0 + nb]
+    ok = p >= 0
+    k = labels[row0 : row0 + nb][ok].to(torch.int64)
+    dst = toff[k] * 16 + p[ok] - offsets[k]
+    x = X[ok]
+    rows_out[dst, : X.shape[1]] = x
+    xf = x.to(torch.float32)
+    cn[dst] = (xf * xf).sum(1)
+
+
+def index_search(index, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: int) -> torch.Tensor:
+    """Sorted search keys int64 [nq, m] (``d2 bits << 32 | row``, ``IVF_EMPTY_KEY`` padded) over
+    the lists of every query's ``nprobe`` nearest centres (:func:`topk`'s indices).  ``d2`` is
+    :func:`topk`'s form with the indexed rows in the place of the centres."""
+    K, dev = index.K, Q.device
+    nq = Q.shape[0]
+    sizes = index.offsets[1:] - index.offsets[:-1]
+    nv = int(index.offsets[K])
+    lid = torch.repeat_interleave(torch.arange(K, dtype=torch.int64, device=dev), sizes)       # list of position p
+    slot = index.tile_offsets[lid] * 16 + torch.arange(nv, dtype=torch.int64, device=dev) - index.offsets[lid]
+    rid = index.order[:nv]
+    store = index.pack.view(-1, index.cols)
+    c = store[slot][:, : Q.shape[1]].to(torch.float32)
+    cn = index.cn[slot]
+    probes = topk(Q, centers, nprobe)[0].to(torch.int64)
+    keys = torch.full((nq, m), IVF_EMPTY_KEY, dtype=torch.int64, device=dev)
+    rows = max(1, (1 << 24) // max(nv, 1))
+    for s in range(0, nq, rows):
+        xb = Q[s : s + rows].to(torch.float32)
+        d = ((xb * xb).sum(1)[:, None] + (cn[None, :] - 2.0 * (xb @ c.T))).clamp_min(0.0) + 0.0   # (-0 -> +0)
+        key = (d.contiguous().view(torch.int32).to(torch.int64) << 32) | rid[None, :]
+        member = torch.zeros((xb.shape[0], K), dtype=torch.bool, device=dev)
+        member.scatter_(1, probes[s : s + rows], True)
+        key = torch.where(member[:, lid], key, IVF_EMPTY_KEY).sort(dim=1).values[:, :m]
+        keys[s : s + rows, : key.shape[1]] = key
+    return keys

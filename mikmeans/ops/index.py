@@ -1,0 +1,178 @@
+"""The fitted clusters as an inverted-file (IVF-Flat) index: nearest-row search through the lists.
+
+* :func:`partition`     rows grouped by label on the device (csrc/ivf.hip: count, scan, scatter)
+* :func:`index_build`   every row's list (:func:`mikmeans.ops.topk` with m = 1), the partition and the
+  rows packed list after list as if they were centres
+* :func:`index_search`  the ``nprobe`` nearest centres of every query, the scan of their lists and
+  the per-query merge: sorted ``(d2 bits << 32 | row)`` keys
+* :func:`index_decode`  keys to ``(rows, squared distances)``
+
+GPU tensors of up to 1024 features run the native kernels; CPU tensors and wider rows run the
+mirrors of :mod:`mikmeans.ops.cpu`, which keep the same lists and the same tensors (the rows in
+natural layout instead of the fragment pack).
+"""
+from __future__ import annotations
+
+import torch
+
+from . import TOPK_NATIVE_MAX, cpu, pad_columns, row_sqnorm, topk, topk_blocks
+from .native import dpad_for, dtype_code, require
+
+__all__ = ["PARTITION_MAX_K", "IVF_EMPTY_KEY", "INDEX_MAX_M", "INDEX_SCAN_KEYS", "partition", "RowIndex",
+           "index_tiles", "index_build", "index_search", "index_decode"]
+
+PARTITION_MAX_K = cpu.PARTITION_MAX_K   # csrc/kernels.h (the extension exports the same number)
+IVF_EMPTY_KEY = cpu.IVF_EMPTY_KEY       # a result slot without a row: behind every key
+INDEX_MAX_M = TOPK_NATIVE_MAX           # the scan kernel's longest list (TOPK_MAX)
+INDEX_SCAN_KEYS = 1 << 27               # keys (8 B each) one scan launch may write: queries go in blocks
+
+
+def partition(labels: torch.Tensor, K: int, *, want_pos: bool = False):
+    """Stable partition of the rows by label: ``(order int64 [n], offsets int64 [K + 1])``.
+    ``order[:offsets[K]]`` holds the rows whose label lies in ``[0, K)``, label after label and
+    ascending within a label -- ``torch.sort(labels[valid], stable=True)``'s permutation -- its tail
+    is -1, and ``offsets`` is the cumulative bincount.  ``want_pos``: also ``rpos`` (int64 [n]),
+    every row's position in ``order`` (-1 for a row in no list).  On the GPU the native count /
+    scan / scatter passes (no atomic decides a position, no host read) for
+    ``K <= PARTITION_MAX_K``; beyond that, and for CPU tensors, a stable ``torch.sort``."""
+    K = int(K)
+    if labels.dim() != 1:
+        raise ValueError("partition needs labels [n]")
+    n = labels.numel()
+    if K < 1 or n >= 1 << 32:
+        raise ValueError(f"partition needs K >= 1 and fewer than 2^32 rows, got K = {K}, n = {n}")
+    if not labels.is_cuda or K > PARTITION_MAX_K:
+        out = cpu.partition(labels, K)
+        return out if want_pos else out[:2]
+    C = require()
+    assert C.PARTITION_MAX_K == PARTITION_MAX_K
+    lab = labels.to(torch.int32).contiguous()
+    dev = lab.device
+    order = torch.empty(n, dtype=torch.int64, device=dev)
+    offsets = torch.empty(K + 1, dtype=torch.int64, device=dev)
+    cells = torch.empty(K * C.partition_blocks(n, K), dtype=torch.int64, device=dev)
+    rpos = torch.empty(n, dtype=torch.int64, device=dev) if want_pos else None
+    C.partition(lab, K, order, offsets, cells, rpos)
+    return (order, offsets, rpos) if want_pos else (order, offsets)
+
+
+def index_tiles(n: int, K: int) -> int:
+    """16-row tiles of an index's row pack: every list padded to whole tiles takes at most
+    ``(n + 15 K) // 16`` of them whatever the list sizes (so the allocation needs no host read)."""
+    return (int(n) + 15 * int(K)) // 16
+
+
+class RowIndex:
+    """The tensors of one index (all on one device):
+
+    ``pack`` the rows, list after list and each list padded to whole 16-row tiles (fragment-packed
+    as :func:`mikmeans.ops.pack_centers` packs centres where ``native``, ``[16 tiles, cols]`` natural
+    rows otherwise), ``cn`` their squared norms, ``order`` (int64 [n], tail -1) the row ids list after
+    list, ``offsets`` / ``tile_offsets`` (int64 [K + 1]) where each list starts in ``order`` / in tiles."""
+
+    def __init__(self, n, K, D, dtype, native, cols, pack, cn, order, offsets, tile_offsets):
+        self.n, self.K, self.D, self.dtype, self.native, self.cols = n, K, D, dtype, native, cols
+        self.pack, self.cn, self.order, self.offsets, self.tile_offsets = pack, cn, order, offsets, tile_offsets
+
+    def tensors(self) -> dict:
+        return {"row_pack": self.pack, "cn": self.cn, "order": self.order, "offsets": self.offsets,
+                "tile_offsets": self.tile_offsets}
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in self.tensors().values())
+
+
+def _native_cols(Xp: torch.Tensor) -> int:
+    return dpad_for(Xp.shape[1], Xp.dtype) if Xp.is_cuda else 0
+
+
+def index_build(X, centers: torch.Tensor, *, pack=None, block_rows: int | None = None, blocks=None,
+                n: int | None = None) -> RowIndex:
+    """Index the rows of ``X`` under ``centers``.  A row's list is :func:`topk`'s first column (the
+    exact nearest centre, the lower index on ties); rows whose distance to it is NaN or infinite are
+    in no list.  ``blocks`` (with ``n``, instead of ``X``): a callable giving an iterator of
+    ``(start, rows, centre pack)`` over the ``n`` rows, walked twice (lists, then the row pack) --
+    host rows cross to the device block by block.  ``block_rows``: rows per top-1 pass.  The index
+    does not depend on either blocking."""
+    if blocks is None:
+        n, blocks = X.shape[0], (lambda: [(0, X, pack)])
+    n, K = int(n), int(centers.shape[0])
+    if n >= 1 << 32:
+        raise ValueError(f"an index takes fewer than 2^32 rows, got {n}")
+    dev = centers.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    shape = None
+    for s, Xt, pk in blocks():
+        Xp = pad_columns(Xt) if Xt.is_cuda else Xt
+        shape = (Xp.shape[1], Xp.dtype, _native_cols(Xp))
+        for s2, idx, d2 in topk_blocks(Xp, centers, 1, pack=pk, block_rows=block_rows):
+            labels[s + s2 : s + s2 + idx.shape[0]] = torch.where(torch.isfinite(d2[:, 0]), idx[:, 0], -1)
+    D, dtype, dpad = shape
+    order, offsets, rpos = partition(labels, K, want_pos=True)
+    sizes = offsets[1:] - offsets[:-1]
+    toff = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    toff[1:] = torch.cumsum((sizes + 15) // 16, 0)
+    cols = dpad or D
+    tiles = index_tiles(n, K)
+    rpack = torch.zeros(tiles * 16 * cols, dtype=dtype, device=dev)
+    cn = torch.full((tiles * 16,), cpu.PAD_SCORE, dtype=torch.float32, device=dev)
+    for s, Xt, _ in blocks():
+        if dpad:
+            require().ivf_pack(pad_columns(Xt), s, labels, rpos, offsets, toff, rpack, cn, dpad)
+        else:
+            cpu.index_pack(Xt, s, labels, rpos, offsets, toff, rpack.view(tiles * 16, cols), cn)
+    return RowIndex(n, K, D, dtype, bool(dpad), cols, rpack, cn, order, offsets, toff)
+
+
+def _scan(index: RowIndex, Qp: torch.Tensor, probes: torch.Tensor, m: int) -> torch.Tensor:
+    """Sorted keys int64 [nq, m] of one block of queries (native)."""
+    C = require()
+    nq, nprobe = probes.shape
+    npairs = nq * nprobe
+    porder, poff = partition(probes.reshape(-1), index.K)      # pair id = q * nprobe + j, grouped by list
+    P = C.ivf_scan_blocks(dtype_code(Qp.dtype), index.cols, m, npairs)
+    per = 16 * P
+    icum = torch.zeros(index.K + 1, dtype=torch.int64, device=Qp.device)
+    icum[1:] = torch.cumsum((poff[1:] - poff[:-1] + per - 1) // per, 0)
+    out = torch.empty((npairs, m), dtype=torch.int64, device=Qp.device)
+    C.ivf_scan(Qp, row_sqnorm(Qp), index.pack, index.cn, index.offsets, index.tile_offsets, index.order, porder, poff,
+               icum, nprobe, index.cols, P, npairs // per + min(index.K, npairs), out)
+    return out.view(nq, nprobe * m).sort(dim=1).values[:, :m]   # unique keys: any sort gives one order
+
+
+def index_search(index: RowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: int, *,
+                 pack=None) -> torch.Tensor:
+    """The ``m`` nearest indexed rows of every query among the lists of its ``nprobe`` nearest centres
+    (:func:`topk`'s indices): int64 keys ``[nq, m]``, ``d2 bits << 32 | row``, ascending -- so equal
+    distances go to the lower row -- and ``IVF_EMPTY_KEY`` where the probed lists hold fewer than
+    ``m`` rows.  ``d2`` is bitwise ``transform(Q, X.float(), squared=True)``'s value for the pair.
+    ``pack``: the centres' pack, as in :func:`topk`."""
+    m, nprobe = int(m), int(nprobe)
+    if not 1 <= m <= INDEX_MAX_M:
+        raise ValueError(f"search needs 1 <= m <= {INDEX_MAX_M}, got m = {m}")
+    if not 1 <= nprobe <= index.K:
+        raise ValueError(f"search needs 1 <= nprobe <= n_clusters ({index.K}), got nprobe = {nprobe}")
+    Qp = pad_columns(Q) if Q.is_cuda else Q
+    if Qp.shape[1] != index.D or Qp.dtype != index.dtype or Qp.device != index.pack.device:
+        raise ValueError(f"search needs queries of {index.D} {index.dtype} features on {index.pack.device}, got "
+                         f"{Qp.shape[1]} {Qp.dtype} on {Qp.device}")
+    nq = Qp.shape[0]
+    if not index.native:
+        return cpu.index_search(index, Qp, centers, m, nprobe)
+    keys = torch.empty((nq, m), dtype=torch.int64, device=Qp.device)
+    block = max(1, INDEX_SCAN_KEYS // (nprobe * m))
+    for s in range(0, nq, block):
+        Qb = Qp[s : s + block]
+        probes, _ = topk(Qb, centers, nprobe, pack=pack)
+        keys[s : s + block] = _scan(index, Qb, probes, m)
+    return keys
+
+
+def index_decode(keys: torch.Tensor, *, row_start: int = 0):
+    """``(rows int64, d2 float32)`` of search keys: each slot's row (plus ``row_start``) and squared
+    distance, -1 and NaN for the empty slots."""
+    empty = keys == IVF_EMPTY_KEY
+    rows = torch.where(empty, -1, (keys & 0xFFFFFFFF) + int(row_start))
+    d2 = torch.where(empty, 0, keys >> 32).to(torch.int32).view(torch.float32)
+    return rows, torch.where(empty, float("nan"), d2)

@@ -446,6 +446,39 @@ def plan_minibatch(n: int, D: int, K: int, dtype="bfloat16", *, batch_rows: int,
     return pl
 
 
+# ------------------------------------------------------------------------- index
+TOPK_BLOCK_ROWS = 1 << 22        # ops.TOPK_BLOCK_ROWS: rows per top-1 pass
+PT_MAX_BLOCKS, PT_MAX_CELLS = 1024, 1 << 20      # csrc/ivf.hip
+
+
+def partition_blocks(n: int, K: int) -> int:
+    """csrc/ivf.hip partition_blocks: workgroups (and count cells per label) of a partition."""
+    cap = max(1, min(PT_MAX_BLOCKS, PT_MAX_CELLS // max(K, 1)))
+    return max(1, min(_cdiv(n, 1024), cap))
+
+
+def index_tiles(n: int, K: int) -> int:
+    """ops.index_tiles: 16-row tiles of the row pack, every list padded to whole tiles."""
+    return (n + 15 * K) // 16
+
+
+def plan_index(n: int, D: int, K: int, dtype="bfloat16", *, block_rows: int | None = None) -> MemoryPlan:
+    """An index of ``n`` rows (ops.index_build / KMeans.build_index): what it keeps -- the row pack
+    (every list padded to whole 16-row tiles, rows padded to the kernels' width), its ``cn``,
+    ``order`` and the two offset arrays -- and the build's scratch: every row's list and position,
+    one block of top-1 output with its row norms, and the partition's count cells."""
+    es = esize_of(dtype)
+    Dp = padded_cols(D, es)
+    cols = dpad_for(Dp, es) or Dp
+    rows = index_tiles(n, K) * 16
+    p = {"row_pack": _r(rows * cols * es), "cn": _r(rows * 4), "order": _r(n * 8), "offsets": _r((K + 1) * 8),
+         "tile_offsets": _r((K + 1) * 8)}
+    B = min(n, int(block_rows) if block_rows else TOPK_BLOCK_ROWS)
+    tr = {"build": {"labels": _r(n * 4), "row_pos": _r(n * 8), "top1_idx": _r(B * 4), "top1_d2": _r(B * 4),
+                    "top1_xn": _r(B * 4), "top1_labels": _r(B * 4), "partition_cells": _r(K * partition_blocks(n, K) * 8)}}
+    return MemoryPlan("index", n, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
+
+
 # ------------------------------------------------------------------------ budget
 def hbm_budget(device=None) -> int:
     """Bytes a fit on ``device`` may allocate: ``MIKMEANS_HBM_BYTES`` when set, else the free
