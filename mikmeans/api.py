@@ -452,8 +452,12 @@ class _Serving(_Params):
         Distances are Euclidean as in :meth:`transform` (``squared``: the kernel's squared
         values; for the cosine metric between unit rows and unit centres).  On the GPU the
         fused top-m kernel on the serving pack (csrc/topk.hip) -- the ``[n, K]`` distance
-        matrix is never written.  numpy in, numpy out; host rows bound for a GPU model go
-        through in blocks (``block_rows``) as in :meth:`predict`."""
+        matrix is never written.  A row with a NaN or infinite coordinate gets NaN or inf
+        distances, never 0, and a centre with one gets them from every row: such a centre
+        sorts behind every finite distance (inf, then NaN).  The folds that read this
+        (:meth:`cluster_report`, :meth:`cluster_exemplars`, :meth:`cluster_quantiles`,
+        :meth:`build_index`) leave such rows out.  numpy in, numpy out; host rows bound for a
+        GPU model go through in blocks (``block_rows``) as in :meth:`predict`."""
         self._check_fitted()
         m = int(m)
         K = int(self.cluster_centers_.shape[0])
@@ -594,7 +598,9 @@ class _Serving(_Params):
     def transform(self, X):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine
         metric, between unit rows and unit centres: sqrt(2 - 2 cos)).  On the GPU: the MFMA
-        transform kernel on the serving pack (csrc/transform.hip)."""
+        transform kernel on the serving pack (csrc/transform.hip).  A row or a centre with a NaN
+        or infinite coordinate gives NaN or inf in its row or column, never 0, and changes no
+        other entry."""
         self._check_fitted()
         Xt, was_numpy = self._inputs(X)
         d = ops.transform(Xt, self.cluster_centers_, pack=self._serving_pack(Xt))
@@ -995,12 +1001,17 @@ class KMeans(_Serving):
     def predict(self, X, *, unassign_nonfinite: bool = False):
         """Nearest-centre labels.  ``unassign_nonfinite`` gives rows with NaN/inf
         coordinates the label -1 ("unassigned", the reference's unassigned list,
-        app.mjs:421-433); the M-step ignores such labels."""
+        app.mjs:421-433); the M-step ignores such labels.  So does a row whose float32
+        squared norm overflows (a coordinate of 1e20): its distance to every centre is inf,
+        :meth:`predict_topk` and the folds treat it as non-finite, and no centre is its
+        nearest.  Without the flag the labels of such rows are unspecified; the other rows
+        keep theirs either way."""
         self._check_fitted()
         labels, _, was_numpy = self._assign_rows(X, False)
         if unassign_nonfinite:
             Xt = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X)
-            bad = (~torch.isfinite(Xt).all(dim=1)).to(labels.device)
+            # (a NaN or infinite coordinate makes the sum of squares NaN or inf as well)
+            bad = (~torch.isfinite(Xt.to(torch.float32).square().sum(dim=1))).to(labels.device)
             labels = labels.masked_fill(bad, -1)
         return labels.cpu().numpy() if was_numpy else labels
 

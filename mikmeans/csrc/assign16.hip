@@ -759,6 +759,10 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
         if (a.track_changed) changed += (old != k);
         a.labels[oi] = k;
         if (a.xn || a.slots) {
+          // fmaxf, not common.h clamp_d2: a NaN sum becomes 0 here on purpose.  inert goes
+          // through slot_add's fixed-point digits, which cannot carry a NaN; the labels, mind
+          // and inertia of rows with non-finite coordinates are unspecified (the transform and
+          // top-m kernels are the ones that report such rows).  The same below.
           const float d = fmaxf(xv + v, 0.f);
           inert += d;
           if (a.mind) a.mind[oi] = d;
@@ -1169,7 +1173,7 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
         v -= offp;   // back to |c|^2 - 2 x.c
         if (a.track_changed) changed += (eold != k);
         __builtin_amdgcn_raw_buffer_store_b32((unsigned)k, rL, (uint32_t)lr * 4u, 0, 0);
-        const float d = fmaxf(exn[0] + v, 0.f);
+        const float d = fmaxf(exn[0] + v, 0.f);   // (fmaxf on purpose: see the epilogue above)
         inert += d;
         if (a.mind) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(d), rM, (uint32_t)lr * 4u, 0, 0);
       }
@@ -1241,7 +1245,7 @@ __global__ __launch_bounds__(256) void split_finish_kernel(AssignArgs a) {
     if (a.track_changed) changed = a.labels[i] != k;
     a.labels[i] = k;
     if (a.xn) {
-      const float d = fmaxf(a.xn[i] + v, 0.f);
+      const float d = fmaxf(a.xn[i] + v, 0.f);   // (fmaxf on purpose: see the assign epilogue)
       inert = d;
       if (a.mind) a.mind[i] = d;
     }

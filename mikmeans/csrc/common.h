@@ -144,6 +144,24 @@ __device__ __forceinline__ float max2f(float a, float b) {
   return d;
 }
 
+// The squared distance |x|^2 + (|c|^2 - 2 x.c) as the transform, top-m and index-scan kernels
+// give it out: a negative sum (rounding) and -0 become +0, every positive value -- +inf too --
+// keeps its bits, and NaN stays NaN, as the one quiet pattern 0x7fc00000, so that a row or a
+// centre with a NaN or infinite coordinate never comes out at distance 0.  (Not fmaxf(v, 0.f):
+// it returns its non-NaN operand, +0 for a NaN sum.)  The bits of a result order as unsigned
+// integers: finite values < +inf < NaN < the all-ones pattern the register lists keep for an
+// empty slot (topk.h TK_EMPTY).
+__device__ __forceinline__ float clamp_d2(float v) {
+  // Two VALU instructions and no compare: gfx950's v_maximum3_f32 (the IEEE 754-2019 maximum:
+  // a NaN operand gives NaN, -0 < +0), then v_min_u32 on the bits, which takes every NaN --
+  // quiet ones are at or above 0x7fc00000, negative ones above 0xff800000 -- to the one pattern
+  // and leaves +0 .. +inf alone.  (The select v > 0 ? v : (v == v ? 0 : NaN) compiled to two
+  // exec-mask branches per score, fmaxf + a NaN select to three instructions and a VCC wait:
+  // profiles/r7_05_nonfinite.md.)
+  const uint32_t m = __float_as_uint(__builtin_elementwise_maximum(v, 0.f));
+  return __uint_as_float(m < 0x7fc00000u ? m : 0x7fc00000u);
+}
+
 // (score, centre) as one u64 whose unsigned order is (score, then lower index): the
 // float's bits mapped to an order-preserving u32 in the high word.
 __device__ __forceinline__ unsigned long long split_key(float v, int k) {

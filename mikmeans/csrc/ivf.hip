@@ -26,7 +26,8 @@
 //    list) per lane with the insertion of topk.h; a query's four lanes merge through LDS and lane
 //    r writes the pair's m keys (d2 bits << 32 | row).  d2 is bitwise the transform kernel's value
 //    for (query, row) with the rows packed as centres: the same cn seed, the same MFMA k-step
-//    order, max(xn_q + acc, 0).
+//    order, clamp_d2(xn_q + acc) (common.h: negatives to +0, NaN and +inf kept, so a query with
+//    a NaN or infinite coordinate finds no row at distance 0).
 #include "pack.h"
 #include "topk.h"
 
@@ -280,7 +281,7 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_scan_kernel(IvfScanArgs a) 
     for (int p = 0; p < P; ++p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float d2 = fmaxf(xn[p] + acc[p][e], 0.f);
+        const float d2 = clamp_d2(xn[p] + acc[p][e]);
         // a position past the list's length is an empty candidate: the strict compare never takes it
         const uint32_t c = k0 + e < nl ? __float_as_uint(d2) : TK_EMPTY;
         const int ck = k0 + e;

@@ -25,7 +25,7 @@ template <> struct KMfma<float> {
 };
 
 constexpr int TK_NW = 4;                    // waves per workgroup
-constexpr uint32_t TK_EMPTY = 0xffffffffu;  // list slot without a candidate (above every d2 >= 0)
+constexpr uint32_t TK_EMPTY = 0xffffffffu;  // list slot without a candidate (above every clamp_d2 value)
 constexpr int TK_NOIDX = 0x7fffffff;
 
 // Piece q of a row for lane group g (features [(4q + g)V, +V)); zero past the row's D columns

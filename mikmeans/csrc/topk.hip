@@ -1,18 +1,21 @@
 // mikmeans — the m nearest centres of every row (predict_topk) on the MFMA tiles.
 //
 // dist[i, j], idx[i, j] = the j-th smallest pair (d2[i, k], k) over the K centres, where
-// d2[i, k] = max(|x_i|^2 + |c_k|^2 - 2 x_i.c_k, 0) is bitwise the squared distance the
-// transform kernel stores (csrc/transform.hip: the same fragment pack, the same cn seeds and
-// the same MFMA k-step order), so equal distances go to the lower centre index and the answer
-// is transform(squared) + a stable sort without the [N, K] matrix ever reaching memory.
+// d2[i, k] = clamp_d2(|x_i|^2 + |c_k|^2 - 2 x_i.c_k) (common.h: negatives to +0, NaN kept) is
+// bitwise the squared distance the transform kernel stores (csrc/transform.hip: the same
+// fragment pack, the same cn seeds and the same MFMA k-step order), so equal distances go to
+// the lower centre index and the answer is transform(squared) + a stable sort without the
+// [N, K] matrix ever reaching memory.  A row or centre with a NaN or infinite coordinate gives
+// inf or NaN distances, never 0; they sort behind every finite one (inf, then NaN).
 //
 // Each wave keeps P blocks of 16 rows in registers and walks the centre tiles as the
 // transform does.  Lane (r = l & 15, g = l >> 4) ends tile t with the 4 scores of row r against
 // centres 16t + 4g + {0..3}; instead of storing them it keeps, per row block, a sorted list of
 // its M best (d2 bits, k) in registers: a fully unrolled insertion (static indexing, so the
 // lists never move to scratch), skipped whenever no lane of the wave has a candidate under its
-// current M-th best.  d2 >= +0, so its bit pattern orders as an unsigned integer and the
-// all-ones pattern marks an empty slot (a distance of +inf still sorts in front of it).  A
+// current M-th best.  d2 is >= +0 or the one NaN pattern of clamp_d2, so its bit pattern orders
+// as an unsigned integer and the all-ones pattern marks an empty slot (distances of +inf and
+// NaN still sort in front of it, so every one of the K centres is a candidate).  A
 // lane meets its centres in ascending order and a candidate goes behind every entry it does
 // not beat strictly, so ties keep the lower index.  After the last tile the four lists of a row (lanes r, r + 16,
 // r + 32, r + 48) go through LDS as (d2 bits << 32 | k) keys and lane r merges them in a
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void topk_kernel(TopkArgs a) {
     for (int p = 0; p < P; ++p) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float d2 = fmaxf(xn[p] + acc[p][e], 0.f);
+        const float d2 = clamp_d2(xn[p] + acc[p][e]);
         // a pad centre (k >= K) is an empty candidate: the strict compare never takes it
         const uint32_t c = k0 + e < a.K ? __float_as_uint(d2) : TK_EMPTY;
         const int ck = k0 + e;

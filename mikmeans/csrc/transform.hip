@@ -1,6 +1,8 @@
 // mikmeans — distances of every row to every centre (KMeans.transform) on the MFMA tiles.
 //
-// out[i, k] = sqrt(max(|x_i|^2 + |c_k|^2 - 2 x_i.c_k, 0)), written as f32 [N, K].  The same
+// out[i, k] = sqrt(clamp_d2(|x_i|^2 + |c_k|^2 - 2 x_i.c_k)), written as f32 [N, K]: a negative
+// sum becomes +0, a NaN or +inf one stays (common.h), so a row or centre with a NaN or infinite
+// coordinate gives NaN or inf distances, never 0.  The same
 // fragment-packed centres the assign kernel reads (csrc/kernels.h layout "16": -2c in the
 // points' dtype, |c_q|^2 of the quantised centres in f32), so a fitted model's serving pack
 // is reused and the distances are those the assign's argmin ranked: bf16 rows against
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(TR_NW * 64) void transform_kernel(TransformArgs a) 
       float v[4];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float d2 = fmaxf(xn[p] + acc[p][e], 0.f);
+        const float d2 = clamp_d2(xn[p] + acc[p][e]);
         v[e] = a.squared ? d2 : __builtin_sqrtf(d2);
       }
       float* o = a.out + row * a.ldo + k0;

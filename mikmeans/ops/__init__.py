@@ -178,7 +178,9 @@ def transform(X: torch.Tensor, centers: torch.Tensor, *, squared: bool = False,
               pack: "CentroidPack | None" = None) -> torch.Tensor:
     """Distance of every row to every centre, ``[n, K]`` float32 (squared with ``squared``):
     on the GPU the MFMA transform kernel (csrc/transform.hip) on the assign kernel's packed
-    centres -- the distances its argmin ranks; elsewhere the PyTorch reference."""
+    centres -- the distances its argmin ranks; elsewhere the PyTorch reference.  A negative
+    rounded sum becomes +0; a row or centre with a NaN or infinite coordinate gives NaN or inf in
+    its row or column, never 0, and leaves every other entry's bits alone."""
     if not X.is_cuda or dpad_for(pad_columns(X[:1]).shape[1], X.dtype) == 0:
         c = cpu.quantize_centers(centers.to(X.device), X.dtype)
         d = torch.cdist(X.to(torch.float32), c)
@@ -203,7 +205,10 @@ def topk(X: torch.Tensor, centers: torch.Tensor, m: int, *, pack: "CentroidPack 
     stable sort of ``transform(X, centers, squared=True)``, bit for bit.  On the GPU the fused
     MFMA kernel (csrc/topk.hip) keeps the ``m <= 32`` best in registers, so the ``[n, K]``
     matrix is never written; a longer list sorts the transform kernel's distances in row
-    blocks of ~256 MB.  ``pack`` as in :func:`transform`.  Elsewhere the PyTorch reference."""
+    blocks of ~256 MB.  ``pack`` as in :func:`transform`.  Elsewhere the PyTorch reference.
+    Non-finite distances are kept as :func:`transform` gives them (never 0) and sort last, inf
+    before NaN: a row with a NaN or infinite coordinate has a non-finite ``d2[:, 0]`` (its ``idx``
+    are valid centres in an unspecified order), a centre with one is the last of every row's K."""
     m = int(m)
     K = centers.shape[0]
     if not 1 <= m <= K:

@@ -235,6 +235,59 @@ def test_estimators_cluster_report_cpu():
     assert torch.equal(mrep.counts, torch.bincount(mb.predict(X).long(), minlength=4))
 
 
+@pytest.mark.parametrize("dtype", ["float32", "bfloat16"])
+def test_nonfinite_rows_are_left_out_of_every_fold(dtype):
+    """Rows with a NaN or infinite coordinate (one NaN, a NaN in the last column, all +inf, one
+    -inf, one 1e20 whose square overflows) through cluster_report, cluster_quantiles and
+    cluster_exemplars on the mirrors: each equals the call on the finite subset X[keep], row ids
+    mapped back, and the report counts the rows it left out.  (The kernels under the same
+    contract: test_gpu_nonfinite.py; build_index: test_ivf.py.)"""
+    g = torch.Generator().manual_seed(6)
+    n, d, K = 513, 30, 37
+    C = 8.0 * torch.randn(K, d, generator=g)
+    X = (C[(torch.arange(n) % K)[torch.randperm(n, generator=g)]] + 0.25 * torch.randn(n, d, generator=g))
+    X = X.to(getattr(torch, dtype)).float()
+    bad = [0, 15, 16, 277, n - 1]
+    X[0, 3], X[15, d - 1], X[16], X[277, 5], X[n - 1, 7] = NAN, NAN, INF, -INF, 1e20
+    keep = torch.ones(n, dtype=torch.bool)
+    keep[bad] = False
+    ids = keep.nonzero().flatten()
+    km = mikmeans.KMeans(K, device="cpu", dtype=dtype)
+    km.cluster_centers_ = C
+
+    def bits(t):
+        t = torch.as_tensor(t)
+        return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32) if t.is_floating_point() else t
+
+    def folds(Z, **kw):
+        rep = km.cluster_report(Z, **kw)
+        out = {k: getattr(rep, k) for k in ("counts", "cluster_inertia", "radius", "cluster_silhouette", "table")}
+        out["left_out"] = int(rep.n_nonfinite.sum())
+        out["q"], out["qn"] = km.cluster_quantiles(Z, (0, 0.5, 1), **kw)
+        out["near"], out["near_d"] = km.cluster_exemplars(Z, 4, **kw)
+        out["far"], out["far_d"] = km.cluster_exemplars(Z, 4, farthest=True, **kw)
+        return out
+
+    got, sub = folds(X), folds(X[keep])
+    assert got.pop("left_out") == len(bad) and sub.pop("left_out") == 0
+    assert int(got["counts"].sum()) == n - len(bad) and int(got["counts"].min()) > 0
+    words = torch.arange(QW) != 15
+    assert torch.equal(got.pop("table")[:, words], sub.pop("table")[:, words])
+    for side in ("near", "far"):
+        rows = sub.pop(side)
+        assert torch.equal(got.pop(side), torch.where(rows < 0, rows, ids[rows.clamp_min(0)])), side
+    for name, t in got.items():
+        assert torch.equal(bits(t), bits(sub[name])), name
+    assert bool(torch.isfinite(got["q"]).all()) and torch.equal(got["qn"], got["counts"])
+    # any blocking, and NumPy in / NumPy out: the same answers
+    again, host = folds(X, block_rows=77), folds(X.numpy())
+    ref_ = folds(X)
+    for name, t in ref_.items():
+        if name != "left_out":
+            assert torch.equal(bits(again[name]), bits(t)) and torch.equal(bits(host[name]), bits(t)), name
+    assert again["left_out"] == host["left_out"] == len(bad)
+
+
 def test_cosine_model_reports_on_unit_rows():
     X = _blobs(800, 7, 4, seed=9)
     km = mikmeans.KMeans(4, metric="cosine", device="cpu", seed=0, max_iter=10).fit(X)

@@ -45,6 +45,44 @@ def test_cpu_topk_matches_numpy_with_ties():
             ops.topk(torch.as_tensor(X), torch.as_tensor(C), bad)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_cpu_nonfinite_rows_and_centres_are_never_near(dtype):
+    """The contract the kernels share (test_gpu_nonfinite.py): a row with a NaN or infinite
+    coordinate -- one NaN, a NaN in the last column, all +inf, one -inf, one 1e20 whose square
+    overflows -- gets NaN or inf distances, never 0, and changes no other row's bits; a centre
+    with a NaN is the last of every row's K and in no shorter list."""
+    g = torch.Generator().manual_seed(4)
+    n, d, K = 70, 24, 7
+    C = 8.0 * torch.randn(K, d, generator=g)
+    X = (C[torch.arange(n) % K] + 0.25 * torch.randn(n, d, generator=g)).to(dtype)
+    clean = X.clone()
+    bad = [0, 15, 16, 35, n - 1]
+    X[0, 3], X[15, d - 1], X[16], X[35, 5], X[n - 1, 7] = float("nan"), float("nan"), float("inf"), -float("inf"), 1e20
+    clean[bad] = 0
+    keep = torch.ones(n, dtype=torch.bool)
+    keep[bad] = False
+    for squared in (True, False):
+        out, exp = ops.transform(X, C, squared=squared), ops.transform(clean, C, squared=squared)
+        assert not bool(torch.isfinite(out[bad]).any()) and bool(torch.isfinite(exp).all())
+        assert torch.equal(out[keep].view(torch.int32), exp[keep].view(torch.int32))
+    for m in (1, 3, K):
+        (idx, d2), (ei, ed) = ops.topk(X, C, m), ops.topk(clean, C, m)
+        assert not bool(torch.isfinite(d2[bad, 0]).any()) and int(idx.min()) >= 0 and int(idx.max()) < K
+        assert torch.equal(idx[keep], ei[keep]) and torch.equal(d2[keep].view(torch.int32), ed[keep].view(torch.int32))
+    for k in (0, 5, K - 1):
+        C2 = C.clone()
+        C2[k, 2] = float("nan")
+        others = torch.arange(K) != k
+        got, exp = ops.transform(clean, C2, squared=True), ops.transform(clean, C, squared=True)
+        assert bool(got[:, k].isnan().all()) and torch.equal(got[:, others].view(torch.int32), exp[:, others].view(torch.int32))
+        idx, d2 = ops.topk(clean, C2, K)
+        ei, ed = ops.topk(clean, C, K)
+        assert bool((idx[:, K - 1] == k).all()) and bool(d2[:, K - 1].isnan().all())
+        for r in range(n):       # the other centres in the clean order
+            assert idx[r, : K - 1].tolist() == [c for c in ei[r].tolist() if c != k]
+        assert bool(torch.isfinite(d2[:, : K - 1]).all())
+
+
 def _kernels(src_name, kernel, tmp_path):
     """{template arguments: resources} of one kernel's instantiations in a built gfx950 object."""
     from mikmeans import _build
