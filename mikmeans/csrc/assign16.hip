@@ -53,6 +53,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "plan.h"
+#include "tile.h"   // Mfma16, the k-step (nothing else of it: this kernel streams the centres through LDS)
 
 namespace mk {
 
@@ -80,22 +81,6 @@ struct Assign16Cfg {
                 "chunk and the Kpad granule must nest (a wider chunk runs only where Kpad is a multiple of it)");
   static_assert(NQ >= 1, "DPAD too small for the 16x16 layout");
   static_assert(PIECES % NW == 0, "chunk pieces must split evenly over waves");
-};
-
-template <typename T> struct Mfma16;
-template <> struct Mfma16<uint16_t> {
-  __device__ static __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(short8, a),
-                                                   __builtin_bit_cast(short8, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mfma16<float> {
-  __device__ static __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, f32x4 c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
-    return c;
-  }
 };
 
 // Sum of squares of one lane's 16-byte piece.
@@ -1302,7 +1287,7 @@ static void launch16_kt(const AssignArgs& b, const dim3& grid, size_t lds, hipSt
                        dim3(NW_ * 64), lds, s, b);
 }
 
-// The geometries that run the bounded E-step's TOP2 epilogue (launch16_d routes every call
+// The geometries that run the bounded E-step's TOP2 epilogue (assign_geometry routes every call
 // with bounds to them).  With a running (min, second) pair per point block the bf16
 // defaults at D = 64 / 128 / 256 spilled 400-940 VGPRs and ran 5.7x slower
 // (profiles/r4_05_hamerly_ab_top2_spills.log); the state is now the second minimum alone
@@ -1328,7 +1313,7 @@ static void launch16_kp(const AssignArgs& b, const dim3& grid, size_t lds, hipSt
       else
         return launch16_kt<T, DPAD, P, CT_, NBUF_, OCC, NW_, false, PMAJ, true, false>(b, grid, lds, s);
     }
-    return;   // (unreachable: launch16_d sends bounds to a top2_geom geometry)
+    return;   // (unreachable: assign_geometry sends bounds to a top2_geom geometry)
   }
   launch16_kt<T, DPAD, P, CT_, NBUF_, OCC, NW_, VARG, PMAJ, false, false>(b, grid, lds, s);
 }
@@ -1449,7 +1434,7 @@ static hipError_t launch16_t(const AssignArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// Point blocks per wave of the default geometries (launch16_d / launch16_w, see there).
+// Point blocks per wave of the default geometries (assign_geometry, see there).
 template <typename T, int DPAD>
 constexpr int p_narrow() {
   return sizeof(T) == 2 ? (DPAD == 64 ? 8 : DPAD == 256 ? 3 : 4) : (DPAD / 4 / Elem<T>::V >= 8 ? 2 : 4);
@@ -1459,63 +1444,41 @@ constexpr int p_wide() {
   return sizeof(T) == 2 ? (DPAD == 512 || DPAD == 1024 ? 3 : DPAD <= 512 ? 4 : 2) : (DPAD <= 512 ? 2 : 1);
 }
 
-// The workgroup's point count (NW*P*16) must divide parallel/shard.py ROW_ALIGN (1536).
+// A launch geometry as compile-time tags: waves per ring, point blocks per wave, tiles per
+// chunk, ring slots, waves per SIMD the registers must allow.  The workgroup's point count
+// must divide parallel/shard.py ROW_ALIGN (1536).
+template <int NW_, int P_, int CT_, int NBUF_, int OCC_>
+struct Geom {
+  static constexpr int NW = NW_, P = P_, CT = CT_, NBUF = NBUF_, OCC = OCC_;
+  static constexpr int ROWS = NW * P * 16;
+  static_assert(1536 % ROWS == 0, "workgroup points must tile the shard grid");
+};
+
+// Registers of rows per lane of a wide kernel: P blocks x NQ 16-B pieces x 4
 template <typename T, int DPAD>
-static hipError_t launch16_d(const AssignArgs& a, hipStream_t s) {
-  constexpr int CT = chunk_tiles16(sizeof(T), DPAD);
-  // 16 KiB chunks in a 2-slot ring.  A/B on MI355X (one process, interleaved rounds; round 1
-  // profiles/r1_08_*, r1_16_*, r1_17_*, round 2 profiles/r2_04_assign_ab.md):
-  //  * bf16 D=128: 4 point blocks per wave at <= 128 VGPRs (4 waves/SIMD) -- 3 / 5 / 6 / 8 blocks,
-  //    2-3 waves/SIMD, 8/16 waves per ring, 4/8 KiB chunks x 3 slots and next-tile fragment
-  //    loads under the MFMAs are all slower;
-  //  * bf16 D=64: 8 point blocks at 3 waves/SIMD, -5 % against 4 blocks at 4; with the
-  //    value-only argmin (K >= 2048) 4 blocks at 4 waves are 4-9 % slower and 12 blocks at
-  //    2 waves 1-10 % slower (profiles/r3_10_assign_p64_ab.log);
-  //  * bf16 D=256: 3 point blocks at 3 waves/SIMD, -4 % against 2 at 4; streamed A fragments
-  //    (3, 4 or 6 blocks) and a 3-slot ring were slower too (r4_04, r5_67), and were removed;
-  //  * f32: the register file sets 4 (D <= 64) or 2 blocks at one wave per SIMD minimum.
-  constexpr int P = p_narrow<T, DPAD>();
-  constexpr int OCC = sizeof(T) == 2 ? ((DPAD == 64 || DPAD == 256) ? 3 : 4) : 1;
-  static_assert(1536 % (4 * P * 16) == 0, "workgroup points must tile the shard grid");
-  if (a.ub) {   // bounded E-step (TOP2): the geometries of top2_geom
-    // 4 point blocks per wave at D = 64 / 128 (the single-register TOP2 state: 0 / 14 spilled
-    // VGPRs, the latter outside the MFMA loop); a 40-iteration bounded fit at N=2e7 D=128
-    // K=1024 ran 6 % faster than with 2 blocks (profiles/r4_17_top2_geom_ab.md).  A/B switch
-    // V_ASSIGN_TOP2_GEOM: 0 = 2 blocks
-    const bool p4 = variant(V_ASSIGN_TOP2_GEOM) != 0;
-    if constexpr (sizeof(T) == 2 && DPAD == 64) {
-      if (p4) return launch16_t<T, DPAD, 4, CT, 2, 4>(a, s);
-      return launch16_t<T, DPAD, 2, CT, 2, 4>(a, s);
-    }
-    if constexpr (sizeof(T) == 2 && DPAD == 128) {
-      if (p4) return launch16_t<T, DPAD, 4, CT, 2, 4>(a, s);
-      return launch16_t<T, DPAD, 2, CT, 2, 4>(a, s);
-    }
-    if constexpr (sizeof(T) == 2 && DPAD == 256) return launch16_t<T, DPAD, 3, CT, 2, 2, 8>(a, s);
-  }
-  if constexpr (sizeof(T) == 2 && DPAD == 256) {
-    // A/B switch V_ASSIGN_GEOM = 1: 8 waves per ring (half the per-point centre stream and
-    // per-workgroup start-up), 3 point blocks at 2 waves/SIMD -- the bounded E-step's geometry
-    if (variant(V_ASSIGN_GEOM) == 1) return launch16_t<T, DPAD, 3, CT, 2, 2, 8>(a, s);
-  }
-  if constexpr (sizeof(T) == 2 && DPAD == 128) {
-    // A/B switch V_ASSIGN_GEOM: 1 = 8 waves share a ring of 32 KiB chunks (a barrier
-    // every 8 tiles instead of 4), 2 = 8 waves share the 16 KiB ring.  K=1024: -0.4 % / +0.1 %;
-    // K=2048: +4.9 % / +4.4 % (profiles/r3_21_ab_geom128.log), near-tie labels move with
-    // the workgroup's seed offset; the headline's K=1024 keeps 4 waves.
-    // A K sweep keeps 4 waves as the default: 8-wave rings measured +5.0 % at K=2048 but
-    // -5.3 % at 3072 and -5.5 % at 4096 (profiles/r3_33_ab_geom128_ksweep.log).
-    const int gm = variant(V_ASSIGN_GEOM);
-    if (gm == 1 && a.Kpad % (16 * 8) == 0) return launch16_t<T, DPAD, P, 8, 2, OCC, 8>(a, s);
-    if (gm == 2) return launch16_t<T, DPAD, P, CT, 2, OCC, 8>(a, s);
-  }
-  return launch16_t<T, DPAD, P, CT, 2, OCC>(a, s);
+constexpr int C_wide_rows() {
+  return p_wide<T, DPAD>() * (DPAD / 4 / Elem<T>::V) * 4;
 }
 
-int assign16_chunk_tiles(int dtype, int dpad) { return plan::assign16_chunk_tiles(dtype == DT_BF16 ? 2 : 4, dpad); }
-int assign_kpad(int dtype, int dpad, int K) { return plan::assign_kpad(dtype == DT_BF16 ? 2 : 4, dpad, K); }
-int assign_cn_len(int kpad) { return plan::assign_cn_len(kpad); }
-
+// The one geometry choice of the assign: f(Geom) for a launch of (T, DPAD, Kpad), bounded
+// (TOP2, the bounded E-step) or not, under the A/B switches V_ASSIGN_GEOM and
+// V_ASSIGN_TOP2_GEOM.  launch_assign16 launches with it and assign16_block_rows returns its
+// ROWS, so the row block a bf16 seed offset is taken over is the launched workgroup by
+// construction (the bounded E-step's exactness rests on it: tests/test_gpu_bounded.py).
+//
+// Narrow rows (DPAD <= 256): 16 KiB chunks in a 2-slot ring.  A/B on MI355X (one process,
+// interleaved rounds; round 1 profiles/r1_08_*, r1_16_*, r1_17_*, round 2
+// profiles/r2_04_assign_ab.md):
+//  * bf16 D=128: 4 point blocks per wave at <= 128 VGPRs (4 waves/SIMD) -- 3 / 5 / 6 / 8 blocks,
+//    2-3 waves/SIMD, 8/16 waves per ring, 4/8 KiB chunks x 3 slots and next-tile fragment
+//    loads under the MFMAs are all slower;
+//  * bf16 D=64: 8 point blocks at 3 waves/SIMD, -5 % against 4 blocks at 4; with the
+//    value-only argmin (K >= 2048) 4 blocks at 4 waves are 4-9 % slower and 12 blocks at
+//    2 waves 1-10 % slower (profiles/r3_10_assign_p64_ab.log);
+//  * bf16 D=256: 3 point blocks at 3 waves/SIMD, -4 % against 2 at 4; streamed A fragments
+//    (3, 4 or 6 blocks) and a 3-slot ring were slower too (r4_04, r5_67), and were removed;
+//  * f32: the register file sets 4 (D <= 64) or 2 blocks at one wave per SIMD minimum.
+//
 // Wide rows (DPAD 384..1024, e.g. sentence-embedding widths): one centre tile per chunk
 // (12-32 KiB), and as many point blocks as ~256 registers of rows hold -- bf16 4 blocks at
 // 384 features, 2 at 768, f32 2 and 1 -- at one wave per SIMD, or two where the kernel
@@ -1525,92 +1488,73 @@ int assign_cn_len(int kpad) { return plan::assign_cn_len(kpad); }
 // at K=1024, +1.9 % at 4096 against 2 (profiles/r6_53_ab_*.log).  The fragment layout, the
 // seed offsets and the argmin epilogue are the narrow kernels'; only the MFMA issue reads
 // the A fragments one at a time (WIDE in assign16_kernel).
-template <typename T, int DPAD>
-constexpr int C_wide_rows() {   // registers of rows per lane: P blocks x NQ 16-B pieces x 4
-  return p_wide<T, DPAD>() * (DPAD / 4 / Elem<T>::V) * 4;
-}
-template <typename T, int DPAD>
-static hipError_t launch16_w(const AssignArgs& a, hipStream_t s) {
+template <typename T, int DPAD, typename F>
+static auto assign_geometry(int kpad, bool bounded, F&& f) {
   constexpr int CT = chunk_tiles16(sizeof(T), DPAD);
-  static_assert(CT == 1, "wide rows: one tile per chunk");
-  constexpr int P = p_wide<T, DPAD>();
-  static_assert(1536 % (4 * P * 16) == 0, "workgroup points must tile the shard grid");
-  // rows in <= 192 registers: hold the kernel to 2 waves/SIMD (the bounded E-step's D=384
-  // build took 257 VGPRs without the bound)
-  constexpr int OCC = C_wide_rows<T, DPAD>() <= 192 ? 2 : 1;
-  return launch16_t<T, DPAD, P, CT, 2, OCC>(a, s);
+  constexpr bool BF = sizeof(T) == 2;
+  if constexpr (DPAD > 256) {
+    static_assert(CT == 1, "wide rows: one tile per chunk");
+    // rows in <= 192 registers: hold the kernel to 2 waves/SIMD (the bounded E-step's D=384
+    // build took 257 VGPRs without the bound)
+    return f(Geom<4, p_wide<T, DPAD>(), CT, 2, (C_wide_rows<T, DPAD>() <= 192 ? 2 : 1)>{});
+  } else {
+    constexpr int P = p_narrow<T, DPAD>();
+    constexpr int OCC = BF ? ((DPAD == 64 || DPAD == 256) ? 3 : 4) : 1;
+    [[maybe_unused]] const int gm = variant(V_ASSIGN_GEOM);
+    if constexpr (BF && (DPAD == 64 || DPAD == 128)) {
+      // bounded: 4 point blocks per wave (the single-register TOP2 state: 0 / 14 spilled
+      // VGPRs, the latter outside the MFMA loop); a 40-iteration bounded fit at N=2e7 D=128
+      // K=1024 ran 6 % faster than with 2 blocks (profiles/r4_17_top2_geom_ab.md).  A/B switch
+      // V_ASSIGN_TOP2_GEOM: 0 = 2 blocks
+      if (bounded) {
+        if (variant(V_ASSIGN_TOP2_GEOM) != 0) return f(Geom<4, 4, CT, 2, 4>{});
+        return f(Geom<4, 2, CT, 2, 4>{});
+      }
+    }
+    if constexpr (BF && DPAD == 256) {
+      // 8 waves per ring (half the per-point centre stream and per-workgroup start-up), 3 point
+      // blocks at 2 waves/SIMD: the bounded E-step's geometry, and A/B switch V_ASSIGN_GEOM = 1
+      if (bounded || gm == 1) return f(Geom<8, 3, CT, 2, 2>{});
+    }
+    if constexpr (BF && DPAD == 128) {
+      // A/B switch V_ASSIGN_GEOM: 1 = 8 waves share a ring of 32 KiB chunks (a barrier
+      // every 8 tiles instead of 4; where Kpad is whole such chunks), 2 = 8 waves share the
+      // 16 KiB ring.  K=1024: -0.4 % / +0.1 %; K=2048: +4.9 % / +4.4 %
+      // (profiles/r3_21_ab_geom128.log), near-tie labels move with the workgroup's seed
+      // offset; the headline's K=1024 keeps 4 waves.  A K sweep keeps 4 waves as the default:
+      // 8-wave rings measured +5.0 % at K=2048 but -5.3 % at 3072 and -5.5 % at 4096
+      // (profiles/r3_33_ab_geom128_ksweep.log).
+      if (gm == 1 && kpad % (16 * 8) == 0) return f(Geom<8, P, 8, 2, OCC>{});
+      if (gm == 2) return f(Geom<8, P, CT, 2, OCC>{});
+    }
+    return f(Geom<4, P, CT, 2, OCC>{});
+  }
 }
 
-// NW * P * 16 of the geometry launch16_d / launch16_w pick for a call without bounds (the A/B
-// switch V_ASSIGN_GEOM included): the row block each bf16 seed offset is taken over.  The
-// bounded E-step's exactness rests on this (tests/test_gpu_bounded.py, bitwise trajectories).
-template <typename T, int DPAD>
-static int block_rows_t(int kpad) {
-  if constexpr (DPAD > 256) return 4 * p_wide<T, DPAD>() * 16;
-  const int gm = variant(V_ASSIGN_GEOM);
-  if constexpr (sizeof(T) == 2 && DPAD == 256) {
-    if (gm == 1) return 8 * 3 * 16;
-  }
-  if constexpr (sizeof(T) == 2 && DPAD == 128) {
-    if ((gm == 1 && kpad % (16 * 8) == 0) || gm == 2) return 8 * 4 * 16;
-  }
-  return 4 * p_narrow<T, DPAD>() * 16;
-}
+int assign16_chunk_tiles(int dtype, int dpad) { return plan::assign16_chunk_tiles(dtype == DT_BF16 ? 2 : 4, dpad); }
+int assign_kpad(int dtype, int dpad, int K) { return plan::assign_kpad(dtype == DT_BF16 ? 2 : 4, dpad, K); }
+int assign_cn_len(int kpad) { return plan::assign_cn_len(kpad); }
 
 int assign16_block_rows(int dtype, int dpad, int kpad) {
-  if (dtype == DT_BF16) {
-    switch (dpad) {
-      case 32: return block_rows_t<uint16_t, 32>(kpad);
-      case 64: return block_rows_t<uint16_t, 64>(kpad);
-      case 128: return block_rows_t<uint16_t, 128>(kpad);
-      case 256: return block_rows_t<uint16_t, 256>(kpad);
-      case 384: return block_rows_t<uint16_t, 384>(kpad);
-      case 512: return block_rows_t<uint16_t, 512>(kpad);
-      case 768: return block_rows_t<uint16_t, 768>(kpad);
-      case 1024: return block_rows_t<uint16_t, 1024>(kpad);
-    }
-  } else {
-    switch (dpad) {
-      case 16: return block_rows_t<float, 16>(kpad);
-      case 32: return block_rows_t<float, 32>(kpad);
-      case 64: return block_rows_t<float, 64>(kpad);
-      case 128: return block_rows_t<float, 128>(kpad);
-      case 256: return block_rows_t<float, 256>(kpad);
-      case 384: return block_rows_t<float, 384>(kpad);
-      case 512: return block_rows_t<float, 512>(kpad);
-      case 768: return block_rows_t<float, 768>(kpad);
-      case 1024: return block_rows_t<float, 1024>(kpad);
-    }
-  }
-  return 0;
+  int rows = 0;   // (an unknown width)
+  for_width(dtype, dpad, [&](auto t, auto w) {
+    return assign_geometry<typename decltype(t)::type, decltype(w)::value>(kpad, false, [&](auto g) {
+      rows = decltype(g)::ROWS;
+      return 0;
+    });
+  });
+  return rows;
 }
 
 hipError_t launch_assign16(int dtype, int dpad, const AssignArgs& a, hipStream_t s) {
-  if (dtype == DT_BF16) {
-    switch (dpad) {
-      case 32: return launch16_d<uint16_t, 32>(a, s);
-      case 64: return launch16_d<uint16_t, 64>(a, s);
-      case 128: return launch16_d<uint16_t, 128>(a, s);
-      case 256: return launch16_d<uint16_t, 256>(a, s);
-      case 384: return launch16_w<uint16_t, 384>(a, s);
-      case 512: return launch16_w<uint16_t, 512>(a, s);
-      case 768: return launch16_w<uint16_t, 768>(a, s);
-      case 1024: return launch16_w<uint16_t, 1024>(a, s);
-    }
-  } else {
-    switch (dpad) {
-      case 16: return launch16_d<float, 16>(a, s);
-      case 32: return launch16_d<float, 32>(a, s);
-      case 64: return launch16_d<float, 64>(a, s);
-      case 128: return launch16_d<float, 128>(a, s);
-      case 256: return launch16_d<float, 256>(a, s);
-      case 384: return launch16_w<float, 384>(a, s);
-      case 512: return launch16_w<float, 512>(a, s);
-      case 768: return launch16_w<float, 768>(a, s);
-      case 1024: return launch16_w<float, 1024>(a, s);
-    }
-  }
-  return hipErrorInvalidValue;
+  return (hipError_t)for_width(dtype, dpad, [&](auto t, auto w) {
+    using T = typename decltype(t)::type;
+    constexpr int DPAD = decltype(w)::value;
+    return assign_geometry<T, DPAD>(a.Kpad, a.ub != nullptr, [&](auto g) {
+      using G = decltype(g);
+      return launch16_t<T, DPAD, G::P, G::CT, G::NBUF, G::OCC, G::NW>(a, s);
+    });
+  });
 }
 
 }  // namespace mk

@@ -64,6 +64,22 @@ int64_t check_points(const Tensor& X, int dt) {
   TORCH_CHECK(reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0, "mikmeans: X must be 16-B aligned");
   return X.size(0) <= 1 ? X.size(1) : X.stride(0);
 }
+// Points whose D columns fit the kernels' padded width; returns the row stride.
+int64_t check_points_dpad(const Tensor& X, int dt, int64_t dpad) {
+  const int64_t ld = check_points(X, dt);
+  TORCH_CHECK(dpad > 0 && X.size(1) <= dpad, "mikmeans: D exceeds dpad");
+  return ld;
+}
+// The fragment-packed rows the points are multiplied against (kernels.h layout "16"; centres,
+// or an index's rows): pack contiguous in the points' dtype with at least `rows` rows of dpad
+// columns, and their |c|^2 in cn, float32 and at least cn_min long.
+void check_pack(const Tensor& pack, const Tensor& cn, const Tensor& X, int64_t rows, int64_t dpad, int64_t cn_min) {
+  check_cuda(pack, "pack");
+  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == X.scalar_type(),
+              "mikmeans: pack must be contiguous and of the points' dtype");
+  TORCH_CHECK(pack.numel() >= rows * dpad, "mikmeans: pack too small (", pack.numel(), " < ", rows, " x ", dpad, ")");
+  check_f32(cn, "cn", cn_min);
+}
 template <typename T>
 T* opt_ptr(const c10::optional<Tensor>& t) {
   return t.has_value() && t->defined() ? reinterpret_cast<T*>(t->data_ptr()) : nullptr;
@@ -79,7 +95,7 @@ void assign(const Tensor& X, const Tensor& pack, const Tensor& cn, const c10::op
             const c10::optional<Tensor>& ub, const c10::optional<Tensor>& lb, bool scatter,
             const c10::optional<Tensor>& count, const c10::optional<Tensor>& oseed) {
   const int dt = dtype_of(X);
-  const int64_t ldx = check_points(X, dt);
+  const int64_t ldx = check_points_dpad(X, dt, dpad);
   // gathered batch: N logical rows, row i = X[rows[i]] (indices from sample_index: in range
   // by construction -- the binding cannot check them without a device sync)
   const bool gathered = rows.has_value() && rows->defined();
@@ -92,7 +108,6 @@ void assign(const Tensor& X, const Tensor& pack, const Tensor& cn, const c10::op
   TORCH_CHECK(!scatter || gathered, "mikmeans: scatter needs rows");
   const int64_t NO = scatter ? X.size(0) : N;   // per-row outputs / inputs: at rows[i] when scattering
   const int D = (int)X.size(1);
-  TORCH_CHECK(D <= dpad, "mikmeans: D exceeds dpad");
   TORCH_CHECK(mk::assign_kpad(dt, (int)dpad, (int)Kpad) == Kpad, "mikmeans: bad Kpad ", Kpad, " for dpad ",
               dpad);
   const bool bounds = ub.has_value() && ub->defined();
@@ -103,11 +118,7 @@ void assign(const Tensor& X, const Tensor& pack, const Tensor& cn, const c10::op
     TORCH_CHECK(xn.has_value() && !(keys.has_value() && keys->defined()),
                 "mikmeans: bounds need xn and the one-pass grid");
   }
-  check_cuda(pack, "pack");
-  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == X.scalar_type(),
-              "mikmeans: pack dtype must match X");
-  TORCH_CHECK(pack.numel() >= Kpad * dpad, "mikmeans: pack too small");
-  check_f32(cn, "cn", mk::assign_cn_len((int)Kpad));
+  check_pack(pack, cn, X, Kpad, dpad, mk::assign_cn_len((int)Kpad));
   TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kInt && labels.is_contiguous() &&
                   labels.numel() >= NO,
               "mikmeans: labels must be contiguous int32 [N]");
@@ -151,14 +162,10 @@ void assign(const Tensor& X, const Tensor& pack, const Tensor& cn, const c10::op
 void transform(const Tensor& X, const Tensor& pack, const Tensor& cn, int64_t K, int64_t Kpad, int64_t dpad,
                const Tensor& xn, const Tensor& out, bool squared) {
   const int dt = dtype_of(X);
-  const int64_t ldx = check_points(X, dt);
+  const int64_t ldx = check_points_dpad(X, dt, dpad);
   const int64_t N = X.size(0);
-  TORCH_CHECK(X.size(1) <= dpad, "mikmeans: D exceeds dpad");
   TORCH_CHECK(mk::assign_kpad(dt, (int)dpad, (int)K) == Kpad, "mikmeans: bad Kpad ", Kpad);
-  check_cuda(pack, "pack");
-  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == X.scalar_type() && pack.numel() >= Kpad * dpad,
-              "mikmeans: pack must be the points' dtype, [Kpad * dpad]");
-  check_f32(cn, "cn", Kpad);
+  check_pack(pack, cn, X, Kpad, dpad, Kpad);
   check_f32(xn, "xn", N);
   check_cuda(out, "out");
   TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && out.size(0) == N && out.size(1) == K &&
@@ -176,14 +183,10 @@ void transform(const Tensor& X, const Tensor& pack, const Tensor& cn, int64_t K,
 void topk(const Tensor& X, const Tensor& pack, const Tensor& cn, int64_t K, int64_t Kpad, int64_t dpad,
           const Tensor& xn, const Tensor& dist, const Tensor& idx) {
   const int dt = dtype_of(X);
-  const int64_t ldx = check_points(X, dt);
+  const int64_t ldx = check_points_dpad(X, dt, dpad);
   const int64_t N = X.size(0);
-  TORCH_CHECK(X.size(1) <= dpad, "mikmeans: D exceeds dpad");
   TORCH_CHECK(K >= 1 && mk::assign_kpad(dt, (int)dpad, (int)K) == Kpad, "mikmeans: bad Kpad ", Kpad);
-  check_cuda(pack, "pack");
-  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == X.scalar_type() && pack.numel() >= Kpad * dpad,
-              "mikmeans: pack must be the points' dtype, [Kpad * dpad]");
-  check_f32(cn, "cn", Kpad);
+  check_pack(pack, cn, X, Kpad, dpad, Kpad);
   check_f32(xn, "xn", N);
   TORCH_CHECK(dist.dim() == 2 && dist.size(0) == N, "mikmeans: dist must be [N, m]");
   const int64_t m = dist.size(1);
@@ -250,21 +253,18 @@ void partition(const Tensor& labels, int64_t K, const Tensor& order, const Tenso
 void ivf_pack(const Tensor& X, int64_t row0, const Tensor& labels, const Tensor& rpos, const Tensor& offsets,
               const Tensor& toff, const Tensor& pack, const Tensor& cn, int64_t dpad) {
   const int dt = dtype_of(X);
-  const int64_t ldx = check_points(X, dt);
+  const int64_t ldx = check_points_dpad(X, dt, dpad);
   const int64_t nb = X.size(0), n = labels.numel(), K = offsets.numel() - 1;
-  TORCH_CHECK(X.size(1) <= dpad && dpad % (4 * vec_of(dt)) == 0, "mikmeans: D exceeds dpad");
+  TORCH_CHECK(dpad % (4 * vec_of(dt)) == 0, "mikmeans: dpad must be whole 16-B pieces for the four lane groups");
   TORCH_CHECK(row0 >= 0 && row0 + nb <= n, "mikmeans: ivf_pack block outside the index's rows");
   TORCH_CHECK(K >= 1, "mikmeans: offsets must be [K + 1]");
   check_i32(labels, "labels", n);
   check_i64(rpos, "rpos", n);
   check_i64(offsets, "offsets", K + 1);
   check_i64(toff, "toff", K + 1);
-  check_cuda(pack, "pack");
-  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == X.scalar_type() && pack.numel() % (16 * dpad) == 0,
-              "mikmeans: pack must be the points' dtype, whole 16-row tiles of dpad columns");
   // every list padded to whole tiles takes at most (n + 15 K) / 16 tiles
-  TORCH_CHECK(pack.numel() / (16 * dpad) >= (n + 15 * K) / 16, "mikmeans: pack too small");
-  check_f32(cn, "cn", pack.numel() / dpad);
+  check_pack(pack, cn, X, (n + 15 * K) / 16 * 16, dpad, pack.numel() / dpad);
+  TORCH_CHECK(pack.numel() % (16 * dpad) == 0, "mikmeans: pack must be whole 16-row tiles of dpad columns");
   mk::IvfPackArgs a;
   a.X = X.data_ptr(); a.nb = nb; a.D = (int)X.size(1); a.ldx = ldx; a.row0 = row0;
   a.labels = labels.data_ptr<int32_t>(); a.rpos = rpos.data_ptr<int64_t>();
@@ -277,15 +277,12 @@ void ivf_scan(const Tensor& Q, const Tensor& qn, const Tensor& pack, const Tenso
               const Tensor& toff, const Tensor& order, const Tensor& porder, const Tensor& poff, const Tensor& icum,
               int64_t nprobe, int64_t dpad, int64_t P, int64_t max_items, const Tensor& out) {
   const int dt = dtype_of(Q);
-  const int64_t ldq = check_points(Q, dt);
+  const int64_t ldq = check_points_dpad(Q, dt, dpad);
   const int64_t nq = Q.size(0), K = offsets.numel() - 1, npairs = nq * nprobe;
-  TORCH_CHECK(Q.size(1) <= dpad, "mikmeans: D exceeds dpad");
   TORCH_CHECK(K >= 1 && nprobe >= 1 && nprobe <= K, "mikmeans: ivf_scan needs 1 <= nprobe <= K");
   check_f32(qn, "qn", nq);
-  check_cuda(pack, "pack");
-  TORCH_CHECK(pack.is_contiguous() && pack.scalar_type() == Q.scalar_type() && pack.numel() % (16 * dpad) == 0,
-              "mikmeans: pack must be the queries' dtype, whole 16-row tiles of dpad columns");
-  check_f32(cn, "cn", pack.numel() / dpad);
+  check_pack(pack, cn, Q, 0, dpad, pack.numel() / dpad);
+  TORCH_CHECK(pack.numel() % (16 * dpad) == 0, "mikmeans: pack must be whole 16-row tiles of dpad columns");
   check_i64(offsets, "offsets", K + 1);
   check_i64(toff, "toff", K + 1);
   check_i64(order, "order", 0);

@@ -1,0 +1,59 @@
+// mikmeans — the one (dtype, padded width) dispatch of the MFMA distance kernels.
+//
+// Host only and free of HIP types, like plan.h, so tests/native/width_fuzz.cpp builds it with
+// g++ -fsanitize=address,undefined.  There is no width list here: a kernel is instantiated for
+// exactly the widths plan::assign_dpad pads a row to, so a new row width is added there alone.
+// A launcher hands for_width a generic functor:
+//
+//   return (hipError_t)for_width(dtype, dpad, [&](auto t, auto w) {
+//     return launch<typename decltype(t)::type, decltype(w)::value>(args, stream);
+//   });
+#pragma once
+#include <stdint.h>
+
+#include <type_traits>
+#include <utility>
+
+#include "plan.h"
+
+namespace mk {
+
+constexpr int WIDTH_BF16 = 1;    // kernels.h DT_BF16 (static_assert there); any other dtype is f32
+constexpr int WIDTH_MAX = 1024;  // the widest row of plan::assign_dpad
+static_assert(plan::assign_dpad(4, WIDTH_MAX) == WIDTH_MAX && plan::assign_dpad(4, WIDTH_MAX + 1) == 0 &&
+                  plan::assign_dpad(2, WIDTH_MAX) == WIDTH_MAX && plan::assign_dpad(2, WIDTH_MAX + 1) == 0,
+              "WIDTH_MAX is plan::assign_dpad's widest row");
+
+template <typename T> struct TypeTag { using type = T; };
+template <int W> using WidthTag = std::integral_constant<int, W>;
+
+namespace detail {
+// (every padded width is a multiple of 16 elements: one 16-B piece per lane group of f32)
+template <typename T, int W, typename F>
+inline bool width_case(int dpad, F& f, int& r) {
+  if constexpr (plan::assign_dpad(sizeof(T), W) == W) {
+    if (dpad == W) {
+      r = (int)f(TypeTag<T>{}, WidthTag<W>{});
+      return true;
+    }
+  }
+  return false;
+}
+template <typename T, typename F, size_t... I>
+inline int for_width_in(int dpad, F& f, std::index_sequence<I...>) {
+  int r = 1;   // hipErrorInvalidValue
+  (void)(width_case<T, 16 * (int)(I + 1)>(dpad, f, r) || ...);
+  return r;
+}
+}  // namespace detail
+
+// f(TypeTag<T>, WidthTag<DPAD>) for the row type and padded width of (dtype, dpad), and its
+// result (a hipError_t, or 0); hipErrorInvalidValue (1) for a width no kernel is built for.
+template <typename F>
+inline int for_width(int dtype, int dpad, F&& f) {
+  constexpr auto seq = std::make_index_sequence<WIDTH_MAX / 16>{};
+  if (dtype == WIDTH_BF16) return detail::for_width_in<uint16_t>(dpad, f, seq);
+  return detail::for_width_in<float>(dpad, f, seq);
+}
+
+}  // namespace mk

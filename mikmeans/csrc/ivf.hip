@@ -25,9 +25,10 @@
 //    the list's tiles straight from global memory and keeps the M best (d2 bits, position in
 //    list) per lane with the insertion of topk.h; a query's four lanes merge through LDS and lane
 //    r writes the pair's m keys (d2 bits << 32 | row).  d2 is bitwise the transform kernel's value
-//    for (query, row) with the rows packed as centres: the same cn seed, the same MFMA k-step
-//    order, clamp_d2(xn_q + acc) (common.h: negatives to +0, NaN and +inf kept, so a query with
-//    a NaN or infinite coordinate finds no row at distance 0).
+//    for (query, row) with the rows packed as centres: the one tile step of tile.h (negatives to
+//    +0, NaN and +inf kept, so a query with a NaN or infinite coordinate finds no row at distance
+//    0).
+#include "dispatch.h"
 #include "pack.h"
 #include "topk.h"
 
@@ -241,13 +242,7 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_scan_kernel(IvfScanArgs a) 
   for (int p = 0; p < P; ++p) {
     const int slot = p * 16 + r;
     pid[p] = a.porder[p0 + (slot < np ? slot : np - 1)];
-    const int64_t row = pid[p] / a.nprobe;
-    xp[p] = (const T*)a.Q + row * a.ldq + g * V;
-    if constexpr (XREG) {
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) xr[p][q] = load_piece<V>(xp[p], q, g, a.D);
-    }
-    xn[p] = a.qn[row];
+    load_row<T, NQ, XREG>(a.Q, a.ldq, pid[p] / a.nprobe, a.qn, g, a.D, xr[p], xp[p], xn[p]);
   }
   uint32_t bv[P][M];
   int bi[P][M];
@@ -259,55 +254,21 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_scan_kernel(IvfScanArgs a) 
       bi[p][j] = TK_NOIDX;
     }
   }
+  // the list's tiles; a position past its length is an empty candidate
   const int64_t t0 = a.toff[l];
-  const T* pack = (const T*)a.pack + t0 * (NQ * 64 * V);
-  const float* cnl = a.cn + t0 * 16;
-  const int ntile = (nl + 15) / 16;
-  for (int t = 0; t < ntile; ++t) {
-    const f32x4 ci = *(const f32x4*)(cnl + t * 16 + 4 * g);
-    f32x4 acc[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) acc[p] = ci;
-    const T* tp = pack + ((int64_t)t * NQ * 64 + lane) * V;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const u32x4 aq = *(const u32x4*)(tp + (int64_t)q * 64 * V);
-#pragma unroll
-      for (int p = 0; p < P; ++p)
-        acc[p] = KMfma<T>::run(aq, XREG ? xr[p][q] : load_piece<V>(xp[p], q, g, a.D), acc[p]);
-    }
-    const int k0 = t * 16 + 4 * g;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d2 = clamp_d2(xn[p] + acc[p][e]);
-        // a position past the list's length is an empty candidate: the strict compare never takes it
-        const uint32_t c = k0 + e < nl ? __float_as_uint(d2) : TK_EMPTY;
-        const int ck = k0 + e;
-        if (__builtin_amdgcn_ballot_w64(c < bv[p][M - 1]) == 0) continue;
-        tk_insert<M>(bv[p], bi[p], c, ck);
-      }
-    }
-  }
+  tk_scan<T, NQ, P, M, XREG>((const T*)a.pack + t0 * (NQ * 64 * V), a.cn + t0 * 16, 0, (nl + 15) / 16, nl, lane, g, xr,
+                             xp, a.D, xn, bv, bi);
   MK_LDS unsigned long long* ws = (MK_LDS unsigned long long*)sm + wid * (M * 64);
   const int64_t* ord = a.order + o0;
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    tk_stage<M>(ws, lane, bv[p], bi[p]);
-    if (g == 0 && p * 16 + r < np) {
-      long long* out = a.out + pid[p] * a.m;
-      tk_merge4<M>(ws, r, a.m, [&](int j, unsigned long long best) {
-        const uint32_t bits = (uint32_t)(best >> 32);
-        // an empty slot: the largest int64, behind every key in the per-query sort
-        out[j] = bits == TK_EMPTY
-                     ? (long long)IVF_EMPTY_KEY
-                     : (long long)(((unsigned long long)bits << 32) | (uint32_t)ord[(uint32_t)best]);
-      });
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();   // the next block's keys overwrite the slab
-  }
+  tk_merge_rows(ws, lane, np, a.m, bv, bi, [&](int p) {
+    long long* out = a.out + pid[p] * a.m;
+    return [=](int j, unsigned long long best) {
+      const uint32_t bits = (uint32_t)(best >> 32);
+      // an empty slot: the largest int64, behind every key in the per-query sort
+      out[j] = bits == TK_EMPTY ? (long long)IVF_EMPTY_KEY
+                                : (long long)(((unsigned long long)bits << 32) | (uint32_t)ord[(uint32_t)best]);
+    };
+  });
 }
 
 template <typename T, int DPAD, int P, int M>
@@ -342,31 +303,9 @@ hipError_t launch_ivf_scan(int dtype, int dpad, int P, const IvfScanArgs& a, hip
   if (a.npairs <= 0 || a.max_items <= 0) return hipSuccess;
   if (a.K < 1 || a.m < 1 || a.m > TOPK_MAX || a.nprobe < 1 || a.D > dpad) return hipErrorInvalidValue;
   if ((a.max_items + TK_NW - 1) / TK_NW > 0x7fffffff) return hipErrorInvalidValue;
-  if (dtype == DT_BF16) {
-    switch (dpad) {
-      case 32: return launch_is<uint16_t, 32>(P, a, s);
-      case 64: return launch_is<uint16_t, 64>(P, a, s);
-      case 128: return launch_is<uint16_t, 128>(P, a, s);
-      case 256: return launch_is<uint16_t, 256>(P, a, s);
-      case 384: return launch_is<uint16_t, 384>(P, a, s);
-      case 512: return launch_is<uint16_t, 512>(P, a, s);
-      case 768: return launch_is<uint16_t, 768>(P, a, s);
-      case 1024: return launch_is<uint16_t, 1024>(P, a, s);
-    }
-  } else {
-    switch (dpad) {
-      case 16: return launch_is<float, 16>(P, a, s);
-      case 32: return launch_is<float, 32>(P, a, s);
-      case 64: return launch_is<float, 64>(P, a, s);
-      case 128: return launch_is<float, 128>(P, a, s);
-      case 256: return launch_is<float, 256>(P, a, s);
-      case 384: return launch_is<float, 384>(P, a, s);
-      case 512: return launch_is<float, 512>(P, a, s);
-      case 768: return launch_is<float, 768>(P, a, s);
-      case 1024: return launch_is<float, 1024>(P, a, s);
-    }
-  }
-  return hipErrorInvalidValue;
+  return (hipError_t)for_width(dtype, dpad, [&](auto t, auto w) {
+    return launch_is<typename decltype(t)::type, decltype(w)::value>(P, a, s);
+  });
 }
 
 }  // namespace mk

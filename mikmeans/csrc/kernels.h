@@ -7,11 +7,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fold.h"   // the frame constants of the per-cluster folds (FOLD_*)
+#include "dispatch.h"   // for_width: the (dtype, padded width) switch of every launcher that has one
+#include "fold.h"       // the frame constants of the per-cluster folds (FOLD_*)
 
 namespace mk {
 
 enum DType : int { DT_F32 = 0, DT_BF16 = 1 };
+static_assert(DT_BF16 == WIDTH_BF16, "dispatch.h for_width takes these dtype codes");
 
 // Number of f64 accumulation slots the assign kernel spreads its per-workgroup
 // inertia / changed-label partials over (slot = blockIdx % NSLOT, 8 doubles each).
@@ -93,7 +95,8 @@ struct AssignArgs {
 void set_assign_timeline(unsigned long long* buf, int64_t capacity);
 hipError_t launch_assign16(int dtype, int dpad, const AssignArgs& a, hipStream_t s);
 // Rows per workgroup of the full (ungathered, unbounded) assign for this shape: the block its
-// bf16 seed offset is taken over (mirrors launch16_d / launch16_w)
+// bf16 seed offset is taken over (the workgroup of the geometry launch_assign16 picks: both
+// read it off assign_geometry in csrc/assign16.hip)
 int assign16_block_rows(int dtype, int dpad, int kpad);
 // oseed[i] = the full pass's seed offset of row i (block_rows from assign16_block_rows; bf16)
 hipError_t launch_seed_offsets(const float* xn, int64_t n, int block_rows, float* oseed, hipStream_t s);

@@ -138,7 +138,8 @@ inline int update_n_chunks_ks(int ks, int nc_slice) {
 constexpr int chunk_tiles16(int esize, int dpad) {
   return (16 * dpad * esize) >= 16384 ? 1 : 16384 / (16 * dpad * esize);
 }
-inline int assign_dpad(int esize, int D) {
+// (the only list of row widths in C++: dispatch.h instantiates the kernels for what this returns)
+constexpr int assign_dpad(int esize, int D) {
   int d = 4 * (16 / esize);
   while (d < D && d < 256) d *= 2;
   if (D <= d) return d;

@@ -1,38 +1,20 @@
 // mikmeans — the pieces the register-list kernels share (csrc/topk.hip: the m nearest centres of
 // every row; csrc/ivf.hip: the m nearest indexed rows of every (query, probed list) pair): the
-// MFMA k-step, the row-piece load, the per-lane sorted list's insertion and the merge of a row's
-// four lane lists through LDS.
+// candidate loop over a range of tiles (the tile step of tile.h, then the per-lane sorted
+// list's insertion) and the merge of a row's four lane lists through LDS.  What a kernel keeps
+// to itself is how a wave finds its rows and what it writes.
 #pragma once
 #include "common.h"
 #include "kernels.h"
+#include "tile.h"
 
 namespace mk {
-
-template <typename T> struct KMfma;
-template <> struct KMfma<uint16_t> {
-  __device__ static __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, const f32x4& c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(short8, a), __builtin_bit_cast(short8, b), c,
-                                                   0, 0, 0);
-  }
-};
-template <> struct KMfma<float> {
-  __device__ static __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, f32x4 c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      c = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(a[e]), __uint_as_float(b[e]), c, 0, 0, 0);
-    return c;
-  }
-};
 
 constexpr int TK_NW = 4;                    // waves per workgroup
 constexpr uint32_t TK_EMPTY = 0xffffffffu;  // list slot without a candidate (above every clamp_d2 value)
 constexpr int TK_NOIDX = 0x7fffffff;
-
-// Piece q of a row for lane group g (features [(4q + g)V, +V)); zero past the row's D columns
-template <int V, typename T>
-__device__ __forceinline__ u32x4 load_piece(const T* rp, int q, int g, int D) {
-  return (4 * q + g) * V < D ? *(const u32x4*)(rp + 4 * q * V) : u32x4{0u, 0u, 0u, 0u};
-}
+// (A kernel fills its lists with these itself: as one more shared helper the same two loops
+// moved the register allocation of sixteen kernels by 40-50 VGPRs, profiles/r9_01_tile_frame.md.)
 
 // Whether a wave's rows stay in registers (4 NQ VGPRs a block) beside the list: the kernel is
 // held to the 256 VGPRs of two waves per SIMD, and the M = 32 insertion needs ~140 of them
@@ -107,6 +89,45 @@ __device__ __forceinline__ void tk_merge4(const MK_LDS unsigned long long* ws, i
         hk[q] = hp[q] < M ? ws[hp[q] * 64 + r + 16 * q] : ~0ull;
       }
     }
+  }
+}
+
+// The candidate loop: tiles [t0, t1) of `pack` against the wave's P row blocks, every d2 of
+// tile_d2 offered to its lane's list with its packed row's number k; k >= nvalid (a pad row) is
+// an empty candidate, which the strict compare never takes.  A tile's candidate is skipped
+// where no lane of the wave has it under its current M-th best.
+template <typename T, int NQ, int P, int M, bool XREG>
+__device__ __forceinline__ void tk_scan(const T* pack, const float* cn, int t0, int t1, int nvalid, int lane, int g,
+                                        const u32x4 (&xr)[P][XREG ? NQ : 1], const T* const (&xp)[P], int D,
+                                        const float (&xn)[P], uint32_t (&bv)[P][M], int (&bi)[P][M]) {
+  for (int t = t0; t < t1; ++t) {
+    f32x4 d2[P];
+    tile_d2<T, NQ, P, XREG>(pack, cn, t, lane, g, xr, xp, D, xn, d2);
+    const int k0 = t * 16 + 4 * g;
+#pragma unroll
+    for (int p = 0; p < P; ++p) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t c = k0 + e < nvalid ? __float_as_uint(d2[p][e]) : TK_EMPTY;
+        const int ck = k0 + e;
+        if (__builtin_amdgcn_ballot_w64(c < bv[p][M - 1]) == 0) continue;
+        tk_insert<M>(bv[p], bi[p], c, ck);
+      }
+    }
+  }
+}
+
+// The merge loop: block after block through the wave's LDS slab ws; lane r < 16 merges row
+// 16p + r of the wave's first nrows rows and hands its m keys to emit_for(p)(j, key)
+template <int P, int M, typename EmitFor>
+__device__ __forceinline__ void tk_merge_rows(MK_LDS unsigned long long* ws, int lane, int nrows, int m,
+                                              const uint32_t (&bv)[P][M], const int (&bi)[P][M], EmitFor emit_for) {
+#pragma unroll
+  for (int p = 0; p < P; ++p) {
+    tk_stage<M>(ws, lane, bv[p], bi[p]);
+    if (lane < 16 && p * 16 + lane < nrows) tk_merge4<M>(ws, lane, m, emit_for(p));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // the next block's keys overwrite the slab
   }
 }
 

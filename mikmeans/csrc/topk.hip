@@ -2,8 +2,8 @@
 //
 // dist[i, j], idx[i, j] = the j-th smallest pair (d2[i, k], k) over the K centres, where
 // d2[i, k] = clamp_d2(|x_i|^2 + |c_k|^2 - 2 x_i.c_k) (common.h: negatives to +0, NaN kept) is
-// bitwise the squared distance the transform kernel stores (csrc/transform.hip: the same
-// fragment pack, the same cn seeds and the same MFMA k-step order), so equal distances go to
+// bitwise the squared distance the transform kernel stores (both come out of the one tile step
+// of csrc/tile.h, over the same fragment pack), so equal distances go to
 // the lower centre index and the answer is transform(squared) + a stable sort without the
 // [N, K] matrix ever reaching memory.  A row or centre with a NaN or infinite coordinate gives
 // inf or NaN distances, never 0; they sort behind every finite one (inf, then NaN).
@@ -21,7 +21,8 @@
 // r + 32, r + 48) go through LDS as (d2 bits << 32 | k) keys and lane r merges them in a
 // rolled loop -- once per wave and row block, so its speed matters little -- writing the
 // row's first m winners.
-#include "topk.h"   // the MFMA step, the list insertion and the merge (shared with csrc/ivf.hip)
+#include "dispatch.h"
+#include "topk.h"   // the candidate loop and the merge (shared with csrc/ivf.hip)
 
 namespace mk {
 
@@ -41,14 +42,8 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void topk_kernel(TopkArgs a) {
   float xn[P];
 #pragma unroll
   for (int p = 0; p < P; ++p) {
-    int64_t row = pbase + p * 16 + r;
-    row = row < a.N ? row : a.N - 1;
-    xp[p] = (const T*)a.X + row * a.ldx + g * V;
-    if constexpr (XREG) {
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) xr[p][q] = load_piece<V>(xp[p], q, g, a.D);
-    }
-    xn[p] = a.xn[row];
+    const int64_t row = pbase + p * 16 + r;
+    load_row<T, NQ, XREG>(a.X, a.ldx, row < a.N ? row : a.N - 1, a.xn, g, a.D, xr[p], xp[p], xn[p]);
   }
   uint32_t bv[P][M];
   int bi[P][M];
@@ -60,52 +55,18 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void topk_kernel(TopkArgs a) {
       bi[p][j] = TK_NOIDX;
     }
   }
-  const T* pack = (const T*)a.pack;
-  const int ntile = (a.K + 15) / 16;   // (the pad tiles up to Kpad hold no centre)
-  for (int t = 0; t < ntile; ++t) {
-    const f32x4 ci = *(const f32x4*)(a.cn + t * 16 + 4 * g);
-    f32x4 acc[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) acc[p] = ci;
-    const T* tp = pack + ((int64_t)t * NQ * 64 + lane) * V;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) {
-      const u32x4 aq = *(const u32x4*)(tp + (int64_t)q * 64 * V);
-#pragma unroll
-      for (int p = 0; p < P; ++p)
-        acc[p] = KMfma<T>::run(aq, XREG ? xr[p][q] : load_piece<V>(xp[p], q, g, a.D), acc[p]);
-    }
-    const int k0 = t * 16 + 4 * g;
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d2 = clamp_d2(xn[p] + acc[p][e]);
-        // a pad centre (k >= K) is an empty candidate: the strict compare never takes it
-        const uint32_t c = k0 + e < a.K ? __float_as_uint(d2) : TK_EMPTY;
-        const int ck = k0 + e;
-        if (__builtin_amdgcn_ballot_w64(c < bv[p][M - 1]) == 0) continue;
-        tk_insert<M>(bv[p], bi[p], c, ck);
-      }
-    }
-  }
-  // merge the row's four lists: keys to LDS as [slot][lane] (conflict-free), lane r reads
+  // (the pad tiles up to Kpad hold no centre)
+  tk_scan<T, NQ, P, M, XREG>((const T*)a.pack, a.cn, 0, (a.K + 15) / 16, a.K, lane, g, xr, xp, a.D, xn, bv, bi);
+  const int64_t left = a.N - pbase;
   MK_LDS unsigned long long* ws = (MK_LDS unsigned long long*)sm + wid * (M * 64);
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    tk_stage<M>(ws, lane, bv[p], bi[p]);
-    const int64_t row = pbase + p * 16 + r;
-    if (g == 0 && row < a.N) {
-      float* od = a.dist + row * a.m;
-      int32_t* oi = a.idx + row * a.m;
-      tk_merge4<M>(ws, r, a.m, [&](int j, unsigned long long best) {
-        od[j] = __uint_as_float((uint32_t)(best >> 32));
-        oi[j] = (int32_t)(uint32_t)best;
-      });
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();   // the next block's keys overwrite the slab
-  }
+  tk_merge_rows(ws, lane, (int)(left < P * 16 ? left : P * 16), a.m, bv, bi, [&](int p) {
+    float* od = a.dist + (pbase + p * 16 + r) * a.m;
+    int32_t* oi = a.idx + (pbase + p * 16 + r) * a.m;
+    return [=](int j, unsigned long long best) {
+      od[j] = __uint_as_float((uint32_t)(best >> 32));
+      oi[j] = (int32_t)(uint32_t)best;
+    };
+  });
 }
 
 template <typename T, int DPAD, int P, int M>
@@ -134,31 +95,9 @@ hipError_t launch_topk(int dtype, int dpad, const TopkArgs& a, hipStream_t s) {
   if (a.N <= 0) return hipSuccess;
   if (a.K <= 0 || a.m < 1 || a.m > TOPK_MAX || a.m > a.K) return hipErrorInvalidValue;
   if (a.Kpad % 16 || a.Kpad < a.K || a.D > dpad) return hipErrorInvalidValue;
-  if (dtype == DT_BF16) {
-    switch (dpad) {
-      case 32: return launch_tk<uint16_t, 32>(a, s);
-      case 64: return launch_tk<uint16_t, 64>(a, s);
-      case 128: return launch_tk<uint16_t, 128>(a, s);
-      case 256: return launch_tk<uint16_t, 256>(a, s);
-      case 384: return launch_tk<uint16_t, 384>(a, s);
-      case 512: return launch_tk<uint16_t, 512>(a, s);
-      case 768: return launch_tk<uint16_t, 768>(a, s);
-      case 1024: return launch_tk<uint16_t, 1024>(a, s);
-    }
-  } else {
-    switch (dpad) {
-      case 16: return launch_tk<float, 16>(a, s);
-      case 32: return launch_tk<float, 32>(a, s);
-      case 64: return launch_tk<float, 64>(a, s);
-      case 128: return launch_tk<float, 128>(a, s);
-      case 256: return launch_tk<float, 256>(a, s);
-      case 384: return launch_tk<float, 384>(a, s);
-      case 512: return launch_tk<float, 512>(a, s);
-      case 768: return launch_tk<float, 768>(a, s);
-      case 1024: return launch_tk<float, 1024>(a, s);
-    }
-  }
-  return hipErrorInvalidValue;
+  return (hipError_t)for_width(dtype, dpad, [&](auto t, auto w) {
+    return launch_tk<typename decltype(t)::type, decltype(w)::value>(a, s);
+  });
 }
 
 }  // namespace mk

@@ -144,8 +144,34 @@ def cmd_run(a) -> int:
         t.setdefault("rn", torch.empty(a.n, dtype=torch.float32, device=dev))
         t["m"].row_sqnorm(eng.X, t["rn"])
 
-    fn = {"update": run_update, "blobs": run_blobs, "colstats": run_colstats,
-          "rownorms": run_rownorms}.get(a.what, run_assign)
+    def run_transform(t):  # squared distances to every centre, [n, k]
+        t.setdefault("out", (torch.empty((a.n, a.k), dtype=torch.float32, device=dev),))
+        t["m"].transform(eng.X, t["pack"], t["cn"], a.k, t["kpad"], dpad, eng.xn, t["out"][0], True)
+
+    def run_topk(t):       # the --m nearest centres of every row
+        t.setdefault("out", (torch.empty((a.n, a.m), dtype=torch.float32, device=dev),
+                             torch.empty((a.n, a.m), dtype=torch.int32, device=dev)))
+        t["m"].topk(eng.X, t["pack"], t["cn"], a.k, t["kpad"], dpad, eng.xn, *t["out"])
+
+    if a.what == "ivf_scan":   # one index, one set of probes and pairs (the head module's) for every module's scan
+        from mikmeans import ops
+        from mikmeans.ops import index as ix
+
+        index, Q = ix.index_build(eng.X, Cen), eng.X[: a.nq]
+        porder, poff = ix.partition(ops.topk(Q, Cen, a.nprobe)[0].reshape(-1), a.k)
+        npairs = Q.shape[0] * a.nprobe
+        per16 = 16 * mods["head"].ivf_scan_blocks(code, dpad, a.m, npairs)
+        icum = torch.zeros(a.k + 1, dtype=torch.int64, device=dev)
+        icum[1:] = torch.cumsum((poff[1:] - poff[:-1] + per16 - 1) // per16, 0)
+        scan = (Q, ops.row_sqnorm(Q), index.pack, index.cn, index.offsets, index.tile_offsets, index.order, porder,
+                poff, icum, a.nprobe, dpad, per16 // 16, npairs // per16 + min(a.k, npairs))
+
+    def run_ivf_scan(t):   # the --m nearest indexed rows of every (query, probed list) pair
+        t.setdefault("out", (torch.empty((scan[0].shape[0] * a.nprobe, a.m), dtype=torch.int64, device=dev),))
+        t["m"].ivf_scan(*scan, t["out"][0])
+
+    fn = {"update": run_update, "blobs": run_blobs, "colstats": run_colstats, "rownorms": run_rownorms,
+          "transform": run_transform, "topk": run_topk, "ivf_scan": run_ivf_scan}.get(a.what, run_assign)
     for t in per.values():          # warm-up (kernel attributes, code objects)
         fn(t)
     torch.cuda.synchronize()
@@ -166,6 +192,10 @@ def cmd_run(a) -> int:
     if a.what == "rownorms":        # the same bits from every module
         for tag, t in per.items():
             t["same"] = bool(torch.equal(t["rn"], per["head"]["rn"]))
+    if a.what in ("transform", "topk", "ivf_scan"):   # the same bits from every module
+        for tag, t in per.items():
+            t["same"] = all(torch.equal(x.view(torch.int32), y.view(torch.int32))
+                            for x, y in zip(t["out"], per["head"]["out"]))
     if a.what == "update":          # the same integer sums from every module
         red = {tag: (t["slab"].view(t["nch"], -1).sum(0), t["cnt"].view(t["nch"], -1).sum(0)) for tag, t in per.items()}
         for tag, t in per.items():
@@ -173,8 +203,11 @@ def cmd_run(a) -> int:
     out = {"n": a.n, "d": a.d, "k": a.k, "dtype": a.dtype, "what": a.what, "variants": {}}
     for tag, t in per.items():
         med = statistics.median(t["ts"])
+        # a round's own median, and their spread: the box's round-to-round noise
+        rmed = [statistics.median(t["ts"][i : i + a.reps]) for i in range(0, len(t["ts"]), a.reps)]
         out["variants"][tag] = {
             "median_ms": round(med, 4), "min_ms": round(min(t["ts"]), 4),
+            "round_median_spread_ms": round(max(rmed) - min(rmed), 4),
             "tflops": round(2.0 * a.n * a.k * a.d / (med * 1e-3) / 1e12, 1),
             "x_TBps": round(a.n * a.d * (2 if a.dtype == "bf16" else 4) / (med * 1e-3) / 1e12, 2),
             "label_mismatch_vs_head": int((t["lab"] != base["lab"]).sum()) if a.what == "assign" else None,
@@ -199,7 +232,11 @@ def main(argv=None) -> int:
     r.add_argument("--dtype", default="bf16")
     r.add_argument("--rounds", type=int, default=5)
     r.add_argument("--reps", type=int, default=5)
-    r.add_argument("--what", default="assign", choices=["assign", "update", "blobs", "colstats", "rownorms"])
+    r.add_argument("--what", default="assign", choices=["assign", "update", "blobs", "colstats", "rownorms",
+                                                        "transform", "topk", "ivf_scan"])
+    r.add_argument("--m", type=int, default=8, help="topk / ivf_scan: list length")
+    r.add_argument("--nq", type=int, default=10_000, help="ivf_scan: queries (the first rows)")
+    r.add_argument("--nprobe", type=int, default=16, help="ivf_scan: lists probed per query")
     a = ap.parse_args(argv)
     if a.cmd == "build":
         cmd_build(a.ref)

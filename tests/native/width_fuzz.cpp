@@ -1,0 +1,48 @@
+// Host sanitizer harness for the (dtype, padded width) dispatch of csrc/dispatch.h (built by
+// tests/test_native_host.py with -fsanitize=address,undefined).  For both element sizes,
+// for_width must reach a case -- with the matching type and width tags -- for exactly the
+// widths plan::assign_dpad returns over D = 1..1024, and refuse every other width in 1..2048;
+// prints "ok <cases>" or the first violation.
+#include <stdio.h>
+
+#include <set>
+
+#include "dispatch.h"
+
+static int fail(const char* what, long long a, long long b, long long c) {
+  printf("FAIL %s %lld %lld %lld\n", what, a, b, c);
+  return 1;
+}
+
+int main() {
+  long long cases = 0;
+  for (int es : {2, 4}) {
+    const int dtype = es == 2 ? mk::WIDTH_BF16 : 0;
+    std::set<int> widths;
+    for (int D = 1; D <= 1024; ++D) {
+      const int w = mk::plan::assign_dpad(es, D);
+      if (w < D) return fail("assign_dpad below D", es, D, w);
+      widths.insert(w);
+    }
+    for (int dpad = 1; dpad <= 2048; ++dpad) {
+      int calls = 0, got_es = 0, got_w = 0;
+      const int r = mk::for_width(dtype, dpad, [&](auto t, auto w) {
+        ++calls;
+        got_es = (int)sizeof(typename decltype(t)::type);
+        got_w = decltype(w)::value;
+        return 0;
+      });
+      ++cases;
+      if (widths.count(dpad)) {
+        if (r != 0 || calls != 1) return fail("width not reached", es, dpad, r);
+        if (got_es != es || got_w != dpad) return fail("wrong tags", es, dpad, got_w);
+      } else if (r != 1 || calls != 0) {   // (1 = hipErrorInvalidValue)
+        return fail("width not refused", es, dpad, r);
+      }
+    }
+    // a case's own result comes back unchanged
+    if (mk::for_width(dtype, *widths.begin(), [](auto, auto) { return 7; }) != 7) return fail("result", es, 0, 0);
+  }
+  printf("ok %lld\n", cases);
+  return 0;
+}

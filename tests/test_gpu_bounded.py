@@ -92,6 +92,22 @@ def test_gathered_assign_with_seed_offsets_is_the_full_pass(native, d, k):
     random subset of rows writes bitwise the full pass's distances and labels at those rows --
     also where the full pass ranks by value (VARG: D=64 K>=2048, D=32 K>=1024), which the TOP2
     kernel then mirrors with its exact epilogue.  Without the offsets the distances differ."""
+    _gathered_assign_is_the_full_pass(native, d, k)
+
+
+@pytest.mark.parametrize("d,k,g", [(128, 256, 1),    # 8 waves, 32 KiB chunks
+                                   (128, 256, 2),    # 8 waves, 16 KiB chunks
+                                   (128, 192, 1),    # Kpad = 192 is not whole 32 KiB chunks: 4 waves, 256-row blocks
+                                   (256, 64, 1)])    # 8 waves x 3 blocks
+def test_gathered_assign_with_seed_offsets_under_assign_geom(native, kvariant, d, k, g):
+    """The same under the A/B switch V_ASSIGN_GEOM, where the full pass launches other workgroups
+    than by default: the row block of the seed offsets (assign_block_rows) and the launched
+    workgroup come from one geometry choice (csrc/assign16.hip assign_geometry)."""
+    kvariant("assign_geom", g)
+    _gathered_assign_is_the_full_pass(native, d, k)
+
+
+def _gathered_assign_is_the_full_pass(native, d, k):
     from mikmeans.ops import pad_columns
 
     n = 120_000

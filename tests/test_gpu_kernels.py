@@ -781,7 +781,7 @@ def test_assign_value_argmin_d64(native, kvariant, n, outlier, d, k):
     argmin on every row resolvable at fp32 resolution of the seeded score, on the split and
     one-pass grids and in per-point-offset workgroups, and distances of the same accuracy;
     where the packed keys resolve a row, both epilogues agree."""
-    wg = 512 if d == 64 else 256           # workgroup points (csrc/assign16.hip launch16_d)
+    wg = 512 if d == 64 else 256           # workgroup points (csrc/assign16.hip assign_geometry)
     g = torch.Generator().manual_seed(11 + n + d)
     X = torch.randn(n, d, generator=g)
     C = torch.randn(k, d, generator=g) * 0.8

@@ -39,12 +39,10 @@ def test_jsnum_under_asan_ubsan(tmp_path):
         assert s == exp, (v, s, exp)
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
-def test_launch_planning_under_asan_ubsan(tmp_path):
-    """csrc/plan.h (M-step slice width / LDS bytes / chunks, fixed-point exponent, assign
-    Kpad) swept over K in [1, 2^20], D in [1, 256] under ASan + UBSan (VERDICT r1 #9)."""
-    exe = tmp_path / "plan_fuzz"
-    src = os.path.join(ROOT, "tests", "native", "plan_fuzz.cpp")
+def _run_harness(tmp_path, name):
+    """tests/native/<name>.cpp built against csrc with ASan + UBSan and run: it prints "ok <cases>"."""
+    exe = tmp_path / name
+    src = os.path.join(ROOT, "tests", "native", name + ".cpp")
     inc = os.path.join(ROOT, "mikmeans", "csrc")
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", "-I", inc, src, "-o", str(exe)],
@@ -53,3 +51,17 @@ def test_launch_planning_under_asan_ubsan(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     out = subprocess.run([str(exe)], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout[-2000:] + out.stderr[-2000:]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_launch_planning_under_asan_ubsan(tmp_path):
+    """csrc/plan.h (M-step slice width / LDS bytes / chunks, fixed-point exponent, assign
+    Kpad) swept over K in [1, 2^20], D in [1, 256] under ASan + UBSan (VERDICT r1 #9)."""
+    _run_harness(tmp_path, "plan_fuzz")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_width_dispatch_under_asan_ubsan(tmp_path):
+    """csrc/dispatch.h for_width, for both element sizes: a case for exactly the widths
+    plan::assign_dpad returns over D = 1..1024, every other width in 1..2048 refused."""
+    _run_harness(tmp_path, "width_fuzz")
