@@ -705,6 +705,9 @@ void kpp_d2(const Tensor& X, const Tensor& c, bool first, const Tensor& d2, cons
   const int dt = dtype_of(X);
   const int64_t ldx = check_points(X, dt);
   const int64_t N = X.size(0);
+  TORCH_CHECK(X.size(1) >= 1 && X.size(1) <= mk::KPP_MAX_D, "mikmeans: kpp_d2 stages the centre in LDS: at most ",
+              mk::KPP_MAX_D, " columns, got ", X.size(1));
+  TORCH_CHECK(rows_per_block >= 1, "mikmeans: kpp_d2 needs rows_per_block >= 1");
   check_f32(c, "c", X.size(1));
   check_f32(d2, "d2", N);
   const int64_t nb = (N + rows_per_block - 1) / rows_per_block;

@@ -429,6 +429,8 @@ hipError_t launch_wdot(const float* a, const float* b, int64_t n, double* out, d
 // With owner[N] (int32: centre each d2 was measured against) and cc[k] (|c - c_j|^2, from
 // launch_kpp_cc) rows the triangle inequality rules out are not read (bit-identical
 // result); knew >= 0 records the new centre as the owner of rows whose d2 drops.
+// The new centre is staged in LDS, so rows have at most KPP_MAX_D (padded) columns.
+constexpr int KPP_MAX_D = 16376;
 hipError_t launch_kpp_d2(int dtype, const void* X, int64_t N, int D, int64_t ldx, const float* c,
                          int first, float* d2, double* block_sums, int64_t rows_per_block,
                          int nblocks, hipStream_t s, int32_t* owner = nullptr,

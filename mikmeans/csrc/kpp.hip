@@ -36,7 +36,18 @@ constexpr int KPP_NT = 256;
 // for sums of squares), so d2, owner and the block sums are bit-identical to the
 // unpruned pass; only the bytes read change.
 constexpr float KPP_PRUNE = 4.004f;
-constexpr int KPP_CC_LDS = 16384;  // centre-centre distances staged in LDS up to this k
+// LDS of one K5 workgroup: the new centre (D floats, padded to 16 B), in the pruned pass the
+// centre-centre distances behind it, and the static reduction buffer -- kept within the 64 KiB
+// every launch gets without an opt-in.  The distances are staged in LDS while all of it fits
+// (kcc <= 16376 - pad4(D)); past that the kernel gathers them from global memory.  The host's
+// LDS request and the kernel's form both read this one rule.
+constexpr int KPP_LDS_BYTES = 64 * 1024;
+constexpr int KPP_RED_BYTES = KPP_NT / 64 * 8;
+__host__ __device__ inline int kpp_cs_floats(int D) { return (D + 3) & ~3; }
+__host__ __device__ inline bool kpp_cc_in_lds(int D, int kcc) {
+  return (int64_t)kpp_cs_floats(D) + kcc <= (KPP_LDS_BYTES - KPP_RED_BYTES) / 4;
+}
+static_assert(KPP_MAX_D * 4 + KPP_RED_BYTES <= KPP_LDS_BYTES && KPP_MAX_D % 4 == 0, "the centre alone must fit");
 
 // LPR lanes per row (each 16 B per pass over the row), UNR rows in flight per lane group.
 // knew >= 0: the owner of every row whose d2 drops becomes knew (< 0: owner is read only,
@@ -58,8 +69,8 @@ __global__ __launch_bounds__(KPP_NT) void kpp_d2_kernel(const T* __restrict__ X,
   // dependent global load), unless there are too many of them
   // (ccs is addressed through the __shared__ array itself so the gathers below compile to
   // ds_read, not flat loads whose waits would also drain the in-flight row loads)
-  const int cc_off = (D + 3) & ~3;
-  const bool cc_lds = PRUNE && kcc <= KPP_CC_LDS;
+  const int cc_off = kpp_cs_floats(D);
+  const bool cc_lds = PRUNE && kpp_cc_in_lds(D, kcc);
   if constexpr (PRUNE) {
     if (cc_lds)
       for (int j = threadIdx.x; j < kcc; j += KPP_NT) ((float*)smem)[cc_off + j] = cc[j];
@@ -120,8 +131,11 @@ __global__ __launch_bounds__(KPP_NT) void kpp_d2_kernel(const T* __restrict__ X,
       for (int u = 0; u < UNR; ++u) {
         float f[V];
         unpack16(w[u], f, (T*)nullptr);
+        // an explicit fma: left to contraction, the compiler fused some (row slot, element)
+        // pairs and not others, differently in the pruned and the unpruned instantiation, and
+        // the two passes then disagreed in the last bit of a row's distance
 #pragma unroll
-        for (int e = 0; e < V; ++e) { const float df = f[e] - cs[col + e]; acc[u] += df * df; }
+        for (int e = 0; e < V; ++e) { const float df = f[e] - cs[col + e]; acc[u] = __builtin_fmaf(df, df, acc[u]); }
       }
     }
 #pragma unroll
@@ -182,8 +196,9 @@ hipError_t launch_kpp_d2(int dtype, const void* X, int64_t N, int D, int64_t ldx
                          int nblocks, hipStream_t s, int32_t* owner, const float* cc, int kcc,
                          int knew) {
   const bool prune = owner != nullptr && cc != nullptr && !first;
-  size_t lds = ((size_t)D * 4 + 15) / 16 * 16;
-  if (prune && kcc <= KPP_CC_LDS) lds += (size_t)kcc * 4;
+  if (D < 1 || D > KPP_MAX_D) return hipErrorInvalidValue;
+  size_t lds = (size_t)kpp_cs_floats(D) * 4;
+  if (prune && kpp_cc_in_lds(D, kcc)) lds += (size_t)kcc * 4;
   if (dtype == DT_BF16) {
     if (prune)
       launch_kpp_d2_t<uint16_t, true>(X, N, D, ldx, c, 0, d2, block_sums, rows_per_block, nblocks, lds,

@@ -323,13 +323,6 @@ def test_kmeanspp_pruned_is_bitwise_unpruned(native, dtype, d, trials):
     assert torch.equal(a, b)
 
 
-def test_kmeanspp_gpu_cpu_same_seed_same_first_center(native):
-    X = B.make_blobs(5000, 16, 8, seed=1)
-    Cg = mikmeans.kmeans_plusplus(X.to(DEV), 8, seed=7).cpu()
-    Cc = mikmeans.kmeans_plusplus(X, 8, seed=7)
-    torch.testing.assert_close(Cg[0], Cc[0])
-
-
 def test_minibatch_gpu_vs_cpu(native):
     from mikmeans.models.minibatch import MiniBatchEngine
 

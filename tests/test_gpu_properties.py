@@ -114,6 +114,31 @@ def test_col_stats_random_shapes(native, n, d, bf16, sparse, seed):
         assert bool(((a - b).abs() <= tol + 1e-300).all()), key
 
 
+@settings(**{**_SET, "max_examples": 60})
+@given(n=st.integers(1, 20000), d=st.integers(1, 1100), rpb=st.integers(1, 5000), bf16=st.booleans(),
+       second=st.booleans(), offset=st.sampled_from([0.0, 40.0]), seed=st.integers(0, 2**20))
+def test_kpp_d2_random_shapes(native, n, d, rpb, bf16, second, offset, seed):
+    """The k-means++ D^2 pass (first, or first then min against another centre) for any (rows,
+    features, rows per block, dtype): every d2 within the derived f32 bound of the float64
+    distance of the stored values (tests/test_kpp.py d2_bound), block sums the sums of d2."""
+    from .test_gpu_kpp import _check_block_sums, _d2_pass, _first_pass
+    from .test_kpp import d2_bound
+
+    dtype = torch.bfloat16 if bf16 else torch.float32
+    g = torch.Generator().manual_seed(seed)
+    X = ops.pad_columns((torch.randn(n, d, generator=g) * 3 + offset).to(dtype))
+    Xg, Xd = X.to(DEV), X.double()
+    rows = [int(torch.randint(0, n, (1,), generator=g)) for _ in range(2)]
+    refs = [((Xd - Xd[i][None, :]) ** 2).sum(1) for i in rows]
+    d2, bs = _first_pass(native, Xg, X[rows[0]].float().to(DEV), rpb)
+    ref = refs[0]
+    if second:
+        bs = _d2_pass(native, Xg, X[rows[1]].float().to(DEV), False, d2, rpb)
+        ref = torch.minimum(refs[0], refs[1])   # (each within e of its own => the min within e of the min)
+    assert bool(((d2.cpu().double() - ref).abs() <= d2_bound(X.shape[1], ref)).all())
+    _check_block_sums(d2, bs, rpb, exact=False)
+
+
 @settings(**{**_SET, "max_examples": 40})
 @given(n=st.integers(1, 3000), d=st.integers(1, 300), centres=st.integers(1, 64), bf16=st.booleans(),
        i0=st.integers(0, 2**40), seed=st.integers(0, 2**32 - 1))
