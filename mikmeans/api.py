@@ -316,6 +316,107 @@ class ClusterIndex:
         d = d2 if squared else d2.sqrt()
         return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
 
+    def _range_args(self, Q, radius, nprobe, squared):
+        """The checked arguments of a range search: ``(centres, nprobe, r2 float32 [nq] on the CPU)``."""
+        c = self._model.cluster_centers_
+        K = int(c.shape[0])
+        nprobe = int(nprobe)
+        if not 1 <= nprobe <= K:
+            raise ValueError(f"range_search needs 1 <= nprobe <= n_clusters ({K}), got nprobe = {nprobe}")
+        if getattr(Q, "ndim", 2) != 2:
+            raise ValueError(f"Q must be 2-D [n_queries, n_features], got shape {tuple(Q.shape)}")
+        nq = int(Q.shape[0])
+        r = (radius.detach().cpu() if torch.is_tensor(radius) else torch.as_tensor(np.asarray(radius, dtype=np.float64)))
+        if r.dim() > 1 or (r.dim() == 1 and r.shape[0] != nq):
+            raise ValueError(f"radius must be a scalar or one value per query ({nq}), got shape {tuple(r.shape)}")
+        if not bool((torch.isfinite(r) & (r >= 0)).all()):
+            raise ValueError("radius must be finite and non-negative")
+        r = r.to(torch.float32)
+        r2 = r if squared else r * r
+        if not bool(torch.isfinite(r2).all()):
+            raise ValueError("radius squared must be finite in float32")
+        return c, nprobe, r2.expand(nq).contiguous()
+
+    def _range_blocks(self, Q, c, r2, nprobe, **kw):
+        """``ops.index_range`` over the host blocks of ``Q``: a list of per-block results."""
+        dev = c.device
+        return [ops.index_range(self._index, Qt, c, r2[i : i + Qt.shape[0]].to(dev), nprobe, pack=pk, **kw)
+                for i, Qt, pk in self._model._host_blocks(Q)]
+
+    def range_count(self, Q, radius, nprobe: int = 8, squared: bool = False):
+        """How many hits :meth:`range_search` gives every query: int64 ``[nq]``, equal to its
+        ``lims[1:] - lims[:-1]``.  Only the count pass runs: nothing is allocated per hit and no
+        host read is made; in a multi-rank job the ranks' counts are summed by one all-reduce."""
+        c, nprobe, r2 = self._range_args(Q, radius, nprobe, squared)
+        counts = torch.cat(self._range_blocks(Q, c, r2, nprobe, count_only=True))
+        if _allreduce(self._comm) is not None:
+            self._comm.allreduce_(counts)
+        return counts if torch.is_tensor(Q) else counts.cpu().numpy()
+
+    def range_search(self, Q, radius, nprobe: int = 8, squared: bool = False, sort: bool = True,
+                     max_results: int | None = None):
+        """Every indexed row within ``radius`` of each query, among the lists of the query's
+        ``nprobe`` nearest centres: ``(lims int64 [nq + 1], rows int64 [total], distances float32
+        [total])``, query q's hits ``rows[lims[q]:lims[q + 1]]`` (global row ids) and their distances.
+
+        ``radius``: a non-negative finite scalar, or one value per query.  The test is made on
+        squared values: a row is a hit where the kernel's float32 squared distance ``d2`` -- bitwise
+        ``ops.transform(Q, X.float(), squared=True)``'s, as in :meth:`search` -- has ``d2 <= r2``,
+        ``r2 = float32(radius) * float32(radius)`` rounded to float32 (``squared``: ``radius`` is
+        ``r2`` itself and the distances returned are ``d2``; otherwise ``d2.sqrt()``).  ``r2`` must be
+        finite.  A query with a NaN or infinite coordinate has no hits, rows in no list are never
+        hits, and ``nprobe = n_clusters`` is the exact range search over the indexed rows.
+        ``sort``: a query's hits nearest first, equal distances by the lower row id (the order of
+        :meth:`search`); otherwise probe after probe (nearest centre first) and ascending row id
+        within a probe, without a per-query sort.  Both orders are bitwise the same from run to
+        run.  ``max_results``: raise ``ValueError`` if the total number of hits exceeds it, after a
+        count pass of its own and before anything sized by the total is allocated.
+
+        On the GPU (csrc/range.hip): the scan's work items -- one wave per (list, block of queries
+        probing it); a long list is not split over waves -- in two passes, a count per (query, probe)
+        pair and, after a cumulative sum, the fill.  The length of the result is only known after
+        the count, so every block of queries costs one host read of its total; that is inherent to a
+        variable-length result.  In a multi-rank job ``Q`` is the same on every rank and every rank
+        returns the one-rank result on the concatenated shards (the ranks' hits are all-gathered
+        and put in the same order).  numpy in, numpy out; host queries bound for a GPU index go
+        through in blocks."""
+        c, nprobe, r2 = self._range_args(Q, radius, nprobe, squared)
+        grouped = _allreduce(self._comm) is not None
+        nq, dev = int(Q.shape[0]), c.device
+        if max_results is not None:
+            counts = torch.cat(self._range_blocks(Q, c, r2, nprobe, count_only=True))
+            if grouped:
+                self._comm.allreduce_(counts)
+            total = int(counts.sum())
+            if total > int(max_results):
+                raise ValueError(f"range_search found {total} rows, more than max_results = {int(max_results)}")
+        parts = self._range_blocks(Q, c, r2, nprobe, sort=sort and not grouped, want_probe=grouped)
+        counts = torch.cat([p[0][1:] - p[0][:-1] for p in parts])
+        keys = torch.cat([p[1] for p in parts])
+        rows = (keys & 0xFFFFFFFF) + self.row_start
+        bits = keys >> 32
+        if grouped:
+            comm = self._comm
+            qid = torch.repeat_interleave(torch.arange(nq, device=dev), counts, output_size=keys.numel())
+            mine = torch.stack([qid, torch.cat([p[2] for p in parts]), bits, rows])
+            sizes = comm.all_gather(torch.tensor([keys.numel()], dtype=torch.int64, device=dev)).reshape(-1).tolist()
+            buf = torch.zeros((4, max(max(sizes), 1)), dtype=torch.int64, device=dev)
+            buf[:, : keys.numel()] = mine
+            every = comm.all_gather(buf)
+            qid, probe, bits, rows = torch.cat([every[w, :, :s] for w, s in enumerate(sizes)], dim=1)
+            comm.allreduce_(counts)
+            o = torch.argsort(rows, stable=True)                      # by (query, bits | probe rank, row):
+            o = o[torch.argsort((bits if sort else probe)[o], stable=True)]   # stable sorts, last key first
+            o = o[torch.argsort(qid[o], stable=True)]
+            bits, rows = bits[o], rows[o]
+        lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        lims[1:] = torch.cumsum(counts, 0)
+        d2 = bits.to(torch.int32).view(torch.float32)
+        d = d2 if squared else d2.sqrt()
+        if torch.is_tensor(Q):
+            return lims, rows, d
+        return lims.cpu().numpy(), rows.cpu().numpy(), d.cpu().numpy()
+
 
 class _Params:
     """scikit-learn estimator protocol: ``get_params`` / ``set_params`` over the constructor's

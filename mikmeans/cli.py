@@ -9,7 +9,9 @@ Commands (the reference's top-bar controls, app.mjs:240-288, as a CLI):
                   simplified silhouette, Davies-Bouldin), as JSON; ``--exemplars M`` adds every
                   cluster's M nearest (``--farthest``: farthest) rows
 * ``search``   -- the M rows of a dataset nearest each query, through a saved model's clusters
-                  (``--nprobe P`` clusters searched per query; rows and distances as .npz)
+                  (``--nprobe P`` clusters searched per query; rows and distances as .npz), or with
+                  ``--radius R`` in place of ``--top M`` every row within R of each query (lims, rows
+                  and distances as .npz)
 * ``blobs``    -- write a synthetic Gaussian-blob dataset
 * ``room``     -- the trait-card game headless: seed/populate/auto-assign/dashboard/export/import
 * ``session``  -- one participant of a live, replicated room session: found it (hosting the
@@ -191,6 +193,10 @@ def cmd_search(a) -> int:
     comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     km = KMeans.load(a.model, device=comm.device)
     K = int(km.cluster_centers_.shape[0])
+    if (a.top is None) == (a.radius is None):
+        raise SystemExit("search: give one of --top M and --radius R")
+    if a.radius is not None:
+        return _search_radius(a, km, comm)
     if not 1 <= a.top <= ops.INDEX_MAX_M:
         raise SystemExit(f"search: --top must be in [1, {ops.INDEX_MAX_M}], got {a.top}")
     if not 1 <= a.nprobe <= K:
@@ -204,6 +210,33 @@ def cmd_search(a) -> int:
             np.savez(a.output, rows=rows.astype(np.int64), distances=dist.astype(np.float32))
         print(json.dumps({"n_samples": n, "n_queries": int(rows.shape[0]), "top": int(a.top), "nprobe": int(a.nprobe),
                           "found": int((rows >= 0).sum())}))
+    comm.close()
+    return 0
+
+
+def _search_radius(a, km, comm) -> int:
+    """``search --radius R`` (``ClusterIndex.range_search``): every row within R of each query among
+    its ``--nprobe`` clusters; rank 0 writes ``lims`` ([nq + 1] int64), ``rows`` (int64, global row
+    indices) and ``distances`` (float32), query q's hits at ``[lims[q], lims[q + 1])``, nearest first."""
+    import math
+
+    from .utils.io import load_points
+
+    K = int(km.cluster_centers_.shape[0])
+    if not (math.isfinite(a.radius) and a.radius >= 0):
+        raise SystemExit(f"search: --radius must be finite and non-negative, got {a.radius}")
+    if not 1 <= a.nprobe <= K:
+        raise SystemExit(f"search: --nprobe must be in [1, {K}], got {a.nprobe}")
+    X, n, start = load_points(a.input, comm.rank, comm.world)
+    Q = np.load(a.queries, allow_pickle=False)
+    index = km.build_index(X.to(comm.device))
+    lims, rows, dist = index.range_search(Q, a.radius, nprobe=a.nprobe, squared=a.squared)
+    if comm.rank == 0:
+        if a.output:
+            np.savez(a.output, lims=lims.astype(np.int64), rows=rows.astype(np.int64),
+                     distances=dist.astype(np.float32))
+        print(json.dumps({"n_samples": n, "n_queries": int(lims.shape[0] - 1), "radius": float(a.radius),
+                          "nprobe": int(a.nprobe), "found": int(rows.shape[0])}))
     comm.close()
     return 0
 
@@ -480,7 +513,10 @@ def build_parser():
     sp.add_argument("--model", required=True)
     sp.add_argument("--input", required=True, help="the rows to index (.npy / .safetensors / .csv)")
     sp.add_argument("--queries", required=True, help="the query rows (.npy)")
-    sp.add_argument("--top", type=int, required=True, metavar="M", help="rows per query (1..32)")
+    sp.add_argument("--top", type=int, metavar="M", help="rows per query (1..32)")
+    sp.add_argument("--radius", type=float, metavar="R",
+                    help="in place of --top: every row within R of each query (with --squared, R is the squared "
+                         "radius); writes lims, rows and distances")
     sp.add_argument("--nprobe", type=int, default=8, metavar="P",
                     help="clusters searched per query (1..n_clusters; n_clusters = exact search)")
     sp.add_argument("--squared", action="store_true", help="write squared distances")

@@ -306,6 +306,48 @@ void ivf_scan(const Tensor& Q, const Tensor& qn, const Tensor& pack, const Tenso
   hip_check(mk::launch_ivf_scan(dt, (int)dpad, (int)P, a, stream()), "ivf_scan");
 }
 
+// Range search (csrc/range.hip): the count pass (counts alone) or the fill pass (base and keys too)
+void ivf_range(const Tensor& Q, const Tensor& qn, const Tensor& r2, const Tensor& pack, const Tensor& cn,
+               const Tensor& offsets, const Tensor& toff, const Tensor& order, const Tensor& porder, const Tensor& poff,
+               const Tensor& icum, int64_t nprobe, int64_t dpad, int64_t P, int64_t max_items, const Tensor& counts,
+               const c10::optional<Tensor>& base, const c10::optional<Tensor>& keys) {
+  const int dt = dtype_of(Q);
+  const int64_t ldq = check_points_dpad(Q, dt, dpad);
+  const int64_t nq = Q.size(0), K = offsets.numel() - 1, npairs = nq * nprobe;
+  TORCH_CHECK(K >= 1 && nprobe >= 1 && nprobe <= K, "mikmeans: ivf_range needs 1 <= nprobe <= K");
+  check_f32(qn, "qn", nq);
+  check_f32(r2, "r2", nq);
+  check_pack(pack, cn, Q, 0, dpad, pack.numel() / dpad);
+  TORCH_CHECK(pack.numel() % (16 * dpad) == 0, "mikmeans: pack must be whole 16-row tiles of dpad columns");
+  check_i64(offsets, "offsets", K + 1);
+  check_i64(toff, "toff", K + 1);
+  check_i64(order, "order", 0);
+  check_i64(porder, "porder", npairs);
+  check_i64(poff, "poff", K + 1);
+  check_i64(icum, "icum", K + 1);
+  check_i64(counts, "counts", npairs);
+  const bool fill = base.has_value() && base->defined();
+  TORCH_CHECK(fill == (keys.has_value() && keys->defined()), "mikmeans: ivf_range's fill pass takes base and keys");
+  if (fill) {
+    check_i64(*base, "base", npairs);
+    check_i64(*keys, "keys", 0);
+  }
+  TORCH_CHECK(P == mk::ivf_range_blocks(dt, (int)dpad, npairs) || P == 1, "mikmeans: bad ivf_range P ", P);
+  TORCH_CHECK(max_items >= npairs / (16 * P) && max_items <= npairs / (16 * P) + K + 1,
+              "mikmeans: bad ivf_range max_items ", max_items);
+  mk::IvfRangeArgs a;
+  a.Q = Q.data_ptr(); a.D = (int)Q.size(1); a.ldq = ldq; a.qn = qn.data_ptr<float>(); a.r2 = r2.data_ptr<float>();
+  a.pack = pack.data_ptr(); a.cn = cn.data_ptr<float>();
+  a.offsets = offsets.data_ptr<int64_t>(); a.toff = toff.data_ptr<int64_t>(); a.order = order.data_ptr<int64_t>();
+  a.porder = porder.data_ptr<int64_t>(); a.poff = poff.data_ptr<int64_t>(); a.icum = icum.data_ptr<int64_t>();
+  a.K = (int)K; a.nprobe = (int)nprobe; a.npairs = npairs; a.max_items = max_items;
+  a.counts = counts.data_ptr<int64_t>();
+  a.base = fill ? base->data_ptr<int64_t>() : nullptr;
+  a.keys = fill ? reinterpret_cast<long long*>(keys->data_ptr<int64_t>()) : nullptr;
+  a.total = fill ? keys->numel() : 0;
+  hip_check(mk::launch_ivf_range(dt, (int)dpad, (int)P, fill, a, stream()), "ivf_range");
+}
+
 void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {
   TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUALITY_WORDS, "mikmeans: table must be [K, ",
               mk::QUALITY_WORDS, "]");
@@ -1041,6 +1083,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("P"), py::arg("max_items"), py::arg("out"));
   m.def("ivf_scan_blocks", &mk::ivf_scan_blocks);
   m.attr("IVF_EMPTY_KEY") = (int64_t)mk::IVF_EMPTY_KEY;
+  m.def("ivf_range", &ivf_range,
+        "the rows of every (query, probed list) pair within the query's squared radius: the count pass, or with base "
+        "and keys the fill pass ((d2 bits << 32 | row) keys in list order)",
+        py::arg("Q"), py::arg("qn"), py::arg("r2"), py::arg("pack"), py::arg("cn"), py::arg("offsets"), py::arg("toff"),
+        py::arg("order"), py::arg("porder"), py::arg("poff"), py::arg("icum"), py::arg("nprobe"), py::arg("dpad"),
+        py::arg("P"), py::arg("max_items"), py::arg("counts"), py::arg("base") = py::none(),
+        py::arg("keys") = py::none());
+  m.def("ivf_range_blocks", &mk::ivf_range_blocks);
   m.def("quality_accumulate", &quality_accumulate,
         "add the top-2 output's per-cluster quality words into table [K, QUALITY_WORDS] (integer atomics)",
         py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("path") = -1);

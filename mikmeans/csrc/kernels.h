@@ -178,6 +178,34 @@ struct IvfScanArgs {
 int ivf_scan_blocks(int dtype, int dpad, int m, int64_t npairs);
 hipError_t launch_ivf_scan(int dtype, int dpad, int P, const IvfScanArgs& a, hipStream_t s);
 
+// ---- range search through the clusters (csrc/range.hip) -----------------------------------
+// Every row of a pair's list with bits(d2) <= bits(r2[query]), on the scan's work items (pairs
+// grouped by list, icum over ceil(pairs_l / 16 P), P from ivf_range_blocks) and with the scan's
+// d2.  Two launches: the count pass writes counts[pair id] (int64), the fill pass writes pair
+// p's keys (d2 bits << 32 | row) in list order from keys[base[p]] on -- base = the caller's
+// exclusive cumulative sum of counts in pair-id order, total = its end (no key is written at or
+// past it).  r2: one finite non-negative float per query.  Bitwise the same on every launch.
+struct IvfRangeArgs {
+  const void* Q; int D; int64_t ldq;
+  const float* qn;           // |q|^2 per query
+  const float* r2;           // squared radius per query
+  const void* pack; const float* cn;   // the row pack
+  const int64_t* offsets;    // [K + 1] list starts in order
+  const int64_t* toff;       // [K + 1] list starts in tiles
+  const int64_t* order;      // row ids, list after list
+  const int64_t* porder;     // [npairs] pair ids grouped by list
+  const int64_t* poff;       // [K + 1]
+  const int64_t* icum;       // [K + 1]
+  int K; int nprobe;
+  int64_t npairs; int64_t max_items;
+  int64_t* counts;           // [npairs] (count pass)
+  const int64_t* base;       // [npairs] (fill pass)
+  long long* keys;           // [total]  (fill pass)
+  int64_t total;
+};
+int ivf_range_blocks(int dtype, int dpad, int64_t npairs);
+hipError_t launch_ivf_range(int dtype, int dpad, int P, bool fill, const IvfRangeArgs& a, hipStream_t s);
+
 // ---- per-cluster quality table (csrc/quality.hip) ----------------------------------------
 // Folds launch_topk's output (m = 1 or 2) into table[K][QUALITY_WORDS] (u64, only ever added
 // into) with integer atomics: per label the digits of sum a^2 and the row count, the digits of

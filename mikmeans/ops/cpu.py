@@ -342,3 +342,58 @@ def index_search(index, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: 
         key = torch.where(member[:, lid], key, IVF_EMPTY_KEY).sort(dim=1).values[:, :m]
         keys[s : s + rows, : key.shape[1]] = key
     return keys
+
+
+def index_range(index, Q: torch.Tensor, centers: torch.Tensor, r2: torch.Tensor, nprobe: int, *, sort: bool = True,
+                count_only: bool = False, want_probe: bool = False):
+    """Range search in the arithmetic of :func:`index_search`: ``(lims int64 [nq + 1], keys int64
+    [total])``, query q's hits -- the rows of its ``nprobe`` probed lists with ``d2 <= r2[q]`` -- as
+    ``d2 bits << 32 | row`` keys in ``keys[lims[q]:lims[q + 1]]``: ascending (``sort``), or probe
+    after probe and in list order within a probe.  ``count_only``: ``counts int64 [nq]`` alone;
+    ``want_probe``: also every hit's probe rank.  ``r2``: float32 [nq], finite and non-negative (a
+    NaN or infinite ``d2`` is no hit)."""
+    K, dev = index.K, Q.device
+    nq = Q.shape[0]
+    sizes = index.offsets[1:] - index.offsets[:-1]
+    nv = int(index.offsets[K])
+    lid = torch.repeat_interleave(torch.arange(K, dtype=torch.int64, device=dev), sizes)       # list of position p
+    slot = index.tile_offsets[lid] * 16 + torch.arange(nv, dtype=torch.int64, device=dev) - index.offsets[lid]
+    rid = index.order[:nv]
+    store = index.pack.view(-1, index.cols)
+    c = store[slot][:, : Q.shape[1]].to(torch.float32)
+    cn = index.cn[slot]
+    probes = topk(Q, centers, nprobe)[0].to(torch.int64) if nq else torch.zeros((0, nprobe), dtype=torch.int64, device=dev)
+    counts = torch.zeros(nq, dtype=torch.int64, device=dev)
+    keys, ranks = [], []
+    rows = max(1, (1 << 24) // max(nv, 1))
+    for s in range(0, nq, rows):
+        xb = Q[s : s + rows].to(torch.float32)
+        d = ((xb * xb).sum(1)[:, None] + (cn[None, :] - 2.0 * (xb @ c.T))).clamp_min(0.0) + 0.0   # (-0 -> +0)
+        prank = torch.full((xb.shape[0], K), nprobe, dtype=torch.int64, device=dev)            # a list's probe rank
+        prank.scatter_(1, probes[s : s + rows], torch.arange(nprobe, dtype=torch.int64, device=dev).expand(xb.shape[0], -1))
+        pr = prank[:, lid]
+        hit = (pr < nprobe) & (d <= r2[s : s + rows, None])
+        counts[s : s + rows] = hit.sum(1)
+        if count_only:
+            continue
+        q, p = hit.nonzero(as_tuple=True)                                                      # query-major, list order
+        key = (d[q, p].contiguous().view(torch.int32).to(torch.int64) << 32) | rid[p]
+        pr = pr[q, p]
+        if sort:
+            key, o1 = key.sort()
+            o2 = q[o1].sort(stable=True).indices
+            key, pr = key[o2], pr[o1][o2]
+        else:
+            o = (q * nprobe + pr).sort(stable=True).indices                                    # pair after pair
+            key, pr = key[o], pr[o]
+        keys.append(key)
+        ranks.append(pr)
+    if count_only:
+        return counts
+    lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    lims[1:] = torch.cumsum(counts, 0)
+    empty = torch.zeros(0, dtype=torch.int64, device=dev)
+    keys = torch.cat(keys) if keys else empty
+    if want_probe:
+        return lims, keys, (torch.cat(ranks) if ranks else empty)
+    return lims, keys

@@ -5,6 +5,8 @@
   rows packed list after list as if they were centres
 * :func:`index_search`  the ``nprobe`` nearest centres of every query, the scan of their lists and
   the per-query merge: sorted ``(d2 bits << 32 | row)`` keys
+* :func:`index_range`   every row of those lists within a radius of the query (csrc/range.hip: a count
+  pass, a cumulative sum and a fill pass): ``(lims, keys)``, a variable number of keys per query
 * :func:`index_decode`  keys to ``(rows, squared distances)``
 
 GPU tensors of up to 1024 features run the native kernels; CPU tensors and wider rows run the
@@ -19,7 +21,7 @@ from . import TOPK_NATIVE_MAX, cpu, pad_columns, row_sqnorm, topk, topk_blocks
 from .native import dpad_for, dtype_code, require
 
 __all__ = ["PARTITION_MAX_K", "IVF_EMPTY_KEY", "INDEX_MAX_M", "INDEX_SCAN_KEYS", "partition", "RowIndex",
-           "index_tiles", "index_build", "index_search", "index_decode"]
+           "index_tiles", "index_build", "index_search", "index_range", "index_decode"]
 
 PARTITION_MAX_K = cpu.PARTITION_MAX_K   # csrc/kernels.h (the extension exports the same number)
 IVF_EMPTY_KEY = cpu.IVF_EMPTY_KEY       # a result slot without a row: behind every key
@@ -167,6 +169,102 @@ def index_search(index: RowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int
         probes, _ = topk(Qb, centers, nprobe, pack=pack)
         keys[s : s + block] = _scan(index, Qb, probes, m)
     return keys
+
+
+def _range_block(index: RowIndex, Qp: torch.Tensor, probes: torch.Tensor, r2: torch.Tensor, count_only: bool):
+    """``(counts int64 [nq * nprobe], keys int64 [total] or None)`` of one block of queries (native):
+    every (query, probe) pair's hits and, unless ``count_only``, their keys in pair-id order (query
+    after query, probe after probe) and in list order within a pair.  The fill pass costs one host
+    read of the block's total."""
+    C = require()
+    nq, nprobe = probes.shape
+    npairs = nq * nprobe
+    dev = Qp.device
+    porder, poff = partition(probes.reshape(-1), index.K)      # pair id = q * nprobe + j, grouped by list
+    P = C.ivf_range_blocks(dtype_code(Qp.dtype), index.cols, npairs)
+    per = 16 * P
+    icum = torch.zeros(index.K + 1, dtype=torch.int64, device=dev)
+    icum[1:] = torch.cumsum((poff[1:] - poff[:-1] + per - 1) // per, 0)
+    counts = torch.zeros(npairs, dtype=torch.int64, device=dev)
+    args = (Qp, row_sqnorm(Qp), r2, index.pack, index.cn, index.offsets, index.tile_offsets, index.order, porder, poff,
+            icum, nprobe, index.cols, P, npairs // per + min(index.K, npairs), counts)
+    C.ivf_range(*args)
+    if count_only:
+        return counts, None
+    end = torch.cumsum(counts, 0)
+    keys = torch.empty(int(end[-1]), dtype=torch.int64, device=dev)   # (the host read)
+    if keys.numel():
+        C.ivf_range(*args, end - counts, keys)
+    return counts, keys
+
+
+def index_range(index: RowIndex, Q: torch.Tensor, centers: torch.Tensor, r2, nprobe: int, *, pack=None,
+                sort: bool = True, count_only: bool = False, block_queries: int | None = None,
+                want_probe: bool = False):
+    """Every indexed row within a squared radius of each query, among the lists of the query's
+    ``nprobe`` nearest centres (:func:`topk`'s indices): ``(lims int64 [nq + 1], keys int64 [total])``,
+    query q's hits ``keys[lims[q]:lims[q + 1]]`` as ``d2 bits << 32 | row`` (:func:`index_decode`).  A
+    row is a hit where the kernel's float32 ``d2`` -- bitwise ``transform(Q, X.float(),
+    squared=True)``'s value for the pair, as in :func:`index_search` -- has ``d2 <= r2[q]``; ``r2``:
+    one finite non-negative float32 per query (or one for all).  A NaN or infinite ``d2`` is no hit.
+
+    ``sort``: a query's keys ascending (nearest first, equal distances by the lower row: two stable
+    sorts over a block's keys, by key and then by query); otherwise probe after probe, nearest
+    centre first, and in list order (ascending row) within a probe, as the kernel writes them.
+    ``count_only``: the count pass alone, ``counts int64 [nq]`` (``lims[1:] - lims[:-1]``; nothing is
+    allocated per hit and no host read is made).  ``want_probe``: also every hit's probe rank (int64
+    [total]).  Queries go through in blocks of ``block_queries`` (default ``INDEX_SCAN_KEYS //
+    nprobe``) so that a block's pair arrays stay bounded; each block's fill pass costs one host read
+    of its total, which a variable-length result cannot avoid.  A long list is not split over
+    waves.  The result does not depend on the blocking and is bitwise the same from run to run."""
+    nprobe = int(nprobe)
+    if Q.dim() != 2:
+        raise ValueError(f"range search needs queries [nq, D], got shape {tuple(Q.shape)}")
+    if not 1 <= nprobe <= index.K:
+        raise ValueError(f"range search needs 1 <= nprobe <= n_clusters ({index.K}), got nprobe = {nprobe}")
+    Qp = pad_columns(Q) if Q.is_cuda else Q
+    if Qp.shape[1] != index.D or Qp.dtype != index.dtype or Qp.device != index.pack.device:
+        raise ValueError(f"range search needs queries of {index.D} {index.dtype} features on {index.pack.device}, "
+                         f"got {Qp.shape[1]} {Qp.dtype} on {Qp.device}")
+    nq, dev = Qp.shape[0], Qp.device
+    r2 = torch.as_tensor(r2, dtype=torch.float32, device=dev)
+    if r2.dim() > 1 or (r2.dim() == 1 and r2.shape[0] != nq):
+        raise ValueError(f"range search needs one squared radius, or one per query ({nq}), got shape {tuple(r2.shape)}")
+    r2 = r2.expand(nq).contiguous()
+    if nq and not bool((torch.isfinite(r2) & (r2 >= 0)).all()):
+        raise ValueError("range search needs finite non-negative squared radii")
+    if not index.native:
+        return cpu.index_range(index, Qp, centers, r2, nprobe, sort=sort, count_only=count_only, want_probe=want_probe)
+    block = max(1, int(block_queries) if block_queries else INDEX_SCAN_KEYS // nprobe)
+    cq, keys, ranks = [], [], []
+    for s in range(0, nq, block):
+        Qb = Qp[s : s + block]
+        nb = Qb.shape[0]
+        probes, _ = topk(Qb, centers, nprobe, pack=pack)
+        counts, kb = _range_block(index, Qb, probes, r2[s : s + block], count_only)
+        cq.append(counts.view(nb, nprobe).sum(1))
+        if count_only:
+            continue
+        pr = None
+        if want_probe:
+            pr = torch.repeat_interleave(torch.arange(nb * nprobe, device=dev), counts, output_size=kb.numel()) % nprobe
+        if sort:
+            qid = torch.repeat_interleave(torch.arange(nb, device=dev), cq[-1], output_size=kb.numel())
+            kb, o1 = kb.sort()                                    # unique keys: any sort gives one order
+            o2 = qid[o1].sort(stable=True).indices
+            kb = kb[o2]
+            pr = pr[o1][o2] if want_probe else None
+        keys.append(kb)
+        ranks.append(pr)
+    cq = torch.cat(cq) if cq else torch.zeros(0, dtype=torch.int64, device=dev)
+    if count_only:
+        return cq
+    lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+    lims[1:] = torch.cumsum(cq, 0)
+    keys = torch.cat(keys) if keys else torch.zeros(0, dtype=torch.int64, device=dev)
+    if want_probe:
+        return lims, keys, (torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev))
+    return lims, keys
 
 
 def index_decode(keys: torch.Tensor, *, row_start: int = 0):
