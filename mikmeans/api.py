@@ -254,11 +254,168 @@ class ClusterIndex:
     ``list_sizes`` (int64 [K]) and ``offsets`` (int64 [K + 1]): every list's length and where it
     starts in ``order``; ``order``: the row ids, list after list and ascending within a list (rows
     whose distance to their centre is not finite are in no list); ``nbytes``: what the index keeps
-    on its device.  In a multi-rank job the lists hold the rank's shard under global row ids."""
+    on its device.  In a multi-rank job the lists hold the rank's shard under global row ids.
+
+    The index can change and be kept (one-rank jobs): :meth:`add` and :meth:`remove` give rows to and
+    take rows from the lists, :meth:`save` and :meth:`load` keep it on disk.  Row ids are handed out
+    in arrival order and never reused: ``n_rows`` counts the ids handed out (the rows of the build and
+    every row added since), ``n_indexed`` the rows in a list now."""
+
+    FORMAT = "mikmeans-index-v1"
+    TENSORS = "index.safetensors"
+    META = "index.json"
 
     def __init__(self, model, index, row_start: int, comm):
         self._model, self._index, self.row_start, self._comm = model, index, int(row_start), comm
-        self.n_rows = int(index.n)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._index.n)
+
+    @property
+    def n_indexed(self) -> int:
+        return int(self._index.offsets[-1])
+
+    def _one_rank(self, what: str):
+        if _allreduce(self._comm) is not None:
+            raise NotImplementedError(f"ClusterIndex.{what} is not available in a multi-rank job")
+
+    def _check_plan(self, what: str, n_total: int, block_rows=None):
+        """The update's memory plan against the HBM budget (GPU indexes), before anything is allocated."""
+        ix = self._index
+        if not ix.pack.is_cuda:
+            return
+        from .parallel import memplan
+
+        D = int(self._model.cluster_centers_.shape[1])
+        plan = memplan.plan_index_update(ix.n, n_total, D, ix.K, ix.dtype, block_rows=block_rows)
+        plan.budget = memplan.hbm_budget(ix.pack.device)
+        if not plan.fits:
+            raise memplan.HBMCapacityError(f"{what}: {plan.summary()} does not fit")
+
+    def add(self, X, *, block_rows: int | None = None) -> int:
+        """Add the rows of ``X`` to the lists of their nearest centres: returns the first (global)
+        row id of the batch, whose rows take consecutive ids.  A row's list follows the rule of
+        :meth:`KMeans.build_index` (cosine models index unit rows; a row whose distance to its centre
+        is NaN or infinite takes an id and is in no list), and the index afterwards equals, tensor for
+        tensor, the one built over all its rows at once.  Only the new rows meet the centres: the
+        rows already held are copied from the old row pack into the new one (csrc/ivf.hip: the
+        repack), so the old and the new index are both alive for a moment
+        (``memplan.plan_index_update``, checked against the HBM budget up front).  numpy or torch,
+        host or device rows (host rows bound for a GPU index cross in blocks of ``block_rows``).
+        After an exception the index is what it was."""
+        self._one_rank("add")
+        mdl, ix = self._model, self._index
+        c = mdl.cluster_centers_
+        if getattr(X, "ndim", 0) != 2 or int(X.shape[1]) != int(c.shape[1]):
+            raise ValueError(f"add takes rows [n, {int(c.shape[1])}], got shape {tuple(getattr(X, 'shape', ()))}")
+        n1 = int(X.shape[0])
+        if ix.n + n1 >= 1 << 32:
+            raise ValueError(f"an index takes fewer than 2^32 row ids, got {ix.n} + {n1}")
+        self._check_plan("add", ix.n + n1, block_rows)
+        new = ops.index_add(ix, None, c, block_rows=block_rows, n=n1, blocks=lambda: mdl._host_blocks(X, block_rows))
+        self._index = new
+        return self.row_start + ix.n
+
+    def remove(self, ids) -> int:
+        """Take the rows ``ids`` (global row ids, integers, in any order) out of their lists:
+        returns how many left one (the one host read).  Duplicates, ids out of range, ids in no
+        list and ids removed before are ignored; the rows that stay keep their ids and their
+        order, and an id is never handed out again.  The index afterwards equals the one built
+        over the rows that stay.  After an exception the index is what it was."""
+        self._one_rank("remove")
+        ix = self._index
+        t = ids if torch.is_tensor(ids) else torch.as_tensor(np.asarray(ids))
+        if t.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            raise ValueError(f"remove takes integer row ids, got {t.dtype}")
+        self._check_plan("remove", ix.n)
+        new, removed = ops.index_remove(ix, t.reshape(-1).to(device=ix.order.device, dtype=torch.int64) - self.row_start)
+        removed = int(removed)
+        self._index = new
+        return removed
+
+    def save(self, path):
+        """Write the index to the directory ``path``: ``index.safetensors`` (its tensors and the
+        centres its rows were listed under) and ``index.json`` (the format version and ``n``, ``K``,
+        ``D``, ``dtype``, ``native``, ``cols``, ``row_start``)."""
+        import json
+        import os
+        from pathlib import Path
+
+        from safetensors.torch import save_file
+
+        self._one_rank("save")
+        ix = self._index
+        path = Path(path)
+        path.mkdir(parents=True, exist_ok=True)
+        blobs = {k: v.detach().to("cpu").contiguous() for k, v in ix.tensors().items()}
+        blobs["centers"] = self._model.cluster_centers_.detach().to("cpu").contiguous()
+        tmp = path / (self.TENSORS + ".tmp")
+        save_file(blobs, str(tmp))
+        os.replace(tmp, path / self.TENSORS)
+        meta = {"format": self.FORMAT, "n": int(ix.n), "K": int(ix.K), "D": int(ix.D),
+                "dtype": "bfloat16" if ix.dtype == torch.bfloat16 else "float32", "native": bool(ix.native),
+                "cols": int(ix.cols), "row_start": int(self.row_start)}
+        tmpm = path / (self.META + ".tmp")
+        tmpm.write_text(json.dumps(meta))
+        os.replace(tmpm, path / self.META)
+        return path
+
+    @classmethod
+    def saved_at(cls, path) -> bool:
+        """Whether the directory ``path`` holds a saved index."""
+        from pathlib import Path
+
+        return (Path(path) / cls.META).is_file() and (Path(path) / cls.TENSORS).is_file()
+
+    @classmethod
+    def load(cls, path, model, device=None) -> "ClusterIndex":
+        """The index :meth:`save` wrote, for ``model`` (whose fitted centres must be the saved ones,
+        bit for bit, and whose dtype and feature count the index's) on ``device`` (default: the
+        model's).  It searches bit for bit as the saved one.  A fragment-packed (GPU) index loads to
+        a GPU only and a natural-layout one to the CPU only, unless its rows are wider than the
+        kernels."""
+        import json
+        from pathlib import Path
+
+        from safetensors.torch import load_file
+
+        model._check_fitted()
+        comm = getattr(model, "comm", None) or get_comm()
+        if _allreduce(comm) is not None:
+            raise NotImplementedError("ClusterIndex.load is not available in a multi-rank job")
+        path = Path(path)
+        meta = json.loads((path / cls.META).read_text())
+        if meta.get("format") != cls.FORMAT:
+            raise ValueError(f"{path}: not a {cls.FORMAT} index (format {meta.get('format')!r})")
+        c = model.cluster_centers_
+        dev = torch.device(device) if device is not None else c.device
+        ts = load_file(str(path / cls.TENSORS))
+        saved_c = ts.pop("centers")
+        dtype = torch.bfloat16 if meta["dtype"] == "bfloat16" else torch.float32
+        if dtype != model.dtype:
+            raise ValueError(f"the index holds {dtype} rows, the model's dtype is {model.dtype}")
+        if saved_c.shape != c.shape or not torch.equal(saved_c, c.detach().to("cpu")):
+            raise ValueError("the model's cluster_centers_ are not the centres the index was saved under")
+        # what an index built for this model on dev has: stored columns, layout, pack columns
+        F = int(c.shape[1])
+        if dev.type == "cuda":
+            D = int(pad_columns(torch.empty((0, F), dtype=dtype)).shape[1])
+            dpad = native_dpad(F, dtype)
+        else:
+            D, dpad = F, 0
+        if bool(meta["native"]) != bool(dpad):
+            raise ValueError("a fragment-packed (GPU) index cannot be loaded to the CPU" if meta["native"] else
+                             "a natural-layout (CPU) index cannot be loaded to a GPU")
+        if (int(meta["K"]), int(meta["D"]), int(meta["cols"])) != (int(c.shape[0]), D, dpad or D):
+            raise ValueError(f"the index holds {meta['K']} lists of {meta['D']}-feature rows, the model has "
+                             f"{int(c.shape[0])} centres of {F} features")
+        if dev.type != c.device.type:
+            raise ValueError(f"the index would load to {dev}, the model's centres are on {c.device}")
+        ts = {k: v.to(dev) for k, v in ts.items()}
+        index = ops.RowIndex(int(meta["n"]), int(meta["K"]), int(meta["D"]), dtype, bool(meta["native"]),
+                             int(meta["cols"]), ts["row_pack"], ts["cn"], ts["order"], ts["offsets"], ts["tile_offsets"])
+        return cls(model, index, int(meta["row_start"]), comm)
 
     @property
     def offsets(self) -> torch.Tensor:
@@ -695,6 +852,11 @@ class _Serving(_Params):
         index = ops.index_build(None, c, block_rows=block_rows, n=n,
                                 blocks=lambda: self._host_blocks(X, block_rows))
         return ClusterIndex(self, index, start, comm)
+
+    def load_index(self, path) -> ClusterIndex:
+        """The index :meth:`ClusterIndex.save` wrote to ``path``, on this model's device
+        (:meth:`ClusterIndex.load`): the fitted centres must be the ones it was saved under."""
+        return ClusterIndex.load(path, self)
 
     def transform(self, X):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine

@@ -183,13 +183,14 @@ def cmd_report(a) -> int:
 
 def cmd_search(a) -> int:
     """Nearest-row search through a saved model's clusters (``KMeans.build_index`` /
-    ``ClusterIndex.search``): every rank indexes its shard of ``--input``, all ranks search the same
-    ``--queries``, the per-rank lists are merged and rank 0 writes ``rows`` ([nq, M] int64, global
-    row indices, -1 padded) and ``distances`` ([nq, M] float32, NaN padded) to ``--output`` (.npz)."""
+    ``ClusterIndex.search``): every rank indexes its shard of ``--input`` (or, in a one-rank job, loads
+    the saved index of ``--index``), all ranks search the same ``--queries``, the per-rank lists are
+    merged and rank 0 writes ``rows`` ([nq, M] int64, global row indices, -1 padded) and ``distances``
+    ([nq, M] float32, NaN padded) to ``--output`` (.npz)."""
     from . import KMeans, ops
 
-    from .utils.io import load_points
-
+    if (a.input is None) == (a.index is None):
+        raise SystemExit("search: give one of --input X and --index DIR")
     comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     km = KMeans.load(a.model, device=comm.device)
     K = int(km.cluster_centers_.shape[0])
@@ -201,9 +202,8 @@ def cmd_search(a) -> int:
         raise SystemExit(f"search: --top must be in [1, {ops.INDEX_MAX_M}], got {a.top}")
     if not 1 <= a.nprobe <= K:
         raise SystemExit(f"search: --nprobe must be in [1, {K}], got {a.nprobe}")
-    X, n, start = load_points(a.input, comm.rank, comm.world)
+    index, n = _search_index(a, km, comm)
     Q = np.load(a.queries, allow_pickle=False)
-    index = km.build_index(X.to(comm.device))
     rows, dist = index.search(Q, a.top, nprobe=a.nprobe, squared=a.squared)
     if comm.rank == 0:
         if a.output:
@@ -214,22 +214,63 @@ def cmd_search(a) -> int:
     return 0
 
 
+def _search_index(a, km, comm):
+    """``(index, rows)`` of a search: the index built over this rank's shard of ``--input``, or the
+    saved one of ``--index`` (``rows``: the dataset's rows, or the row ids the saved index handed out)."""
+    from .utils.io import load_points
+
+    if a.index is not None:
+        index = km.load_index(a.index)
+        return index, index.n_rows
+    X, n, start = load_points(a.input, comm.rank, comm.world)
+    return km.build_index(X.to(comm.device)), n
+
+
+def cmd_index(a) -> int:
+    """Build, update and keep a saved model's index (``KMeans.build_index``, ``ClusterIndex.add`` /
+    ``remove`` / ``save``): built from ``--input``, or loaded from ``--output`` when that directory
+    already holds one; then the row ids of ``--remove`` (.npy, integers) leave, the rows of ``--add``
+    join, and the index is written to ``--output``.  Prints ``n_rows``, ``n_indexed``, ``added_first_id``,
+    ``removed`` and ``nbytes``."""
+    from . import ClusterIndex, KMeans
+
+    from .utils.io import load_points
+
+    comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
+    km = KMeans.load(a.model, device=comm.device)
+    if a.input is not None:
+        X, n, start = load_points(a.input, comm.rank, comm.world)
+        index = km.build_index(X.to(comm.device))
+    elif ClusterIndex.saved_at(a.output):
+        index = km.load_index(a.output)
+    else:
+        raise SystemExit(f"index: give --input X to build from: {a.output} holds no index")
+    removed = first = None
+    if a.remove is not None:
+        removed = index.remove(np.load(a.remove, allow_pickle=False))
+    if a.add is not None:
+        X2, _, _ = load_points(a.add, 0, 1)
+        first = index.add(X2)
+    index.save(a.output)
+    print(json.dumps({"n_rows": index.n_rows, "n_indexed": index.n_indexed, "added_first_id": first,
+                      "removed": removed, "nbytes": index.nbytes}))
+    comm.close()
+    return 0
+
+
 def _search_radius(a, km, comm) -> int:
     """``search --radius R`` (``ClusterIndex.range_search``): every row within R of each query among
     its ``--nprobe`` clusters; rank 0 writes ``lims`` ([nq + 1] int64), ``rows`` (int64, global row
     indices) and ``distances`` (float32), query q's hits at ``[lims[q], lims[q + 1])``, nearest first."""
     import math
 
-    from .utils.io import load_points
-
     K = int(km.cluster_centers_.shape[0])
     if not (math.isfinite(a.radius) and a.radius >= 0):
         raise SystemExit(f"search: --radius must be finite and non-negative, got {a.radius}")
     if not 1 <= a.nprobe <= K:
         raise SystemExit(f"search: --nprobe must be in [1, {K}], got {a.nprobe}")
-    X, n, start = load_points(a.input, comm.rank, comm.world)
+    index, n = _search_index(a, km, comm)
     Q = np.load(a.queries, allow_pickle=False)
-    index = km.build_index(X.to(comm.device))
     lims, rows, dist = index.range_search(Q, a.radius, nprobe=a.nprobe, squared=a.squared)
     if comm.rank == 0:
         if a.output:
@@ -511,7 +552,8 @@ def build_parser():
     rp.add_argument("--device")
     sp = sub.add_parser("search", help="the rows of a dataset nearest each query, through a saved model's clusters")
     sp.add_argument("--model", required=True)
-    sp.add_argument("--input", required=True, help="the rows to index (.npy / .safetensors / .csv)")
+    sp.add_argument("--input", help="the rows to index (.npy / .safetensors / .csv)")
+    sp.add_argument("--index", metavar="DIR", help="in place of --input: a saved index (mikmeans index) to load")
     sp.add_argument("--queries", required=True, help="the query rows (.npy)")
     sp.add_argument("--top", type=int, metavar="M", help="rows per query (1..32)")
     sp.add_argument("--radius", type=float, metavar="R",
@@ -522,6 +564,14 @@ def build_parser():
     sp.add_argument("--squared", action="store_true", help="write squared distances")
     sp.add_argument("--output", help="write rows and distances here (.npz)")
     sp.add_argument("--device")
+    ip = sub.add_parser("index", help="build, update and save the index of a dataset under a saved model")
+    ip.add_argument("--model", required=True)
+    ip.add_argument("--output", required=True, metavar="DIR", help="the index directory (loaded first if it holds one "
+                                                                    "and no --input is given)")
+    ip.add_argument("--input", help="the rows to index (.npy / .safetensors / .csv)")
+    ip.add_argument("--add", metavar="X2", help="rows to add to the index (.npy / .safetensors / .csv)")
+    ip.add_argument("--remove", metavar="IDS", help="row ids to take out of the index (.npy, integers)")
+    ip.add_argument("--device")
     b = sub.add_parser("blobs", help="write a synthetic dataset")
     b.add_argument("--n", type=int, required=True)
     b.add_argument("--d", type=int, required=True)
@@ -619,7 +669,7 @@ def main(argv=None) -> int:
         a, rest = la.parse_known_args(argv[1:])
         return cmd_launch(a, rest)
     a = build_parser().parse_args(argv)
-    return {"fit": cmd_fit, "predict": cmd_predict, "report": cmd_report, "search": cmd_search, "blobs": cmd_blobs, "room": cmd_room, "session": cmd_session,
+    return {"fit": cmd_fit, "predict": cmd_predict, "report": cmd_report, "search": cmd_search, "index": cmd_index, "blobs": cmd_blobs, "room": cmd_room, "session": cmd_session,
             "export": cmd_export, "import": cmd_import, "info": cmd_info, "plan": cmd_plan,
             "serve": cmd_serve}[a.cmd](a)
 

@@ -273,6 +273,46 @@ void ivf_pack(const Tensor& X, int64_t row0, const Tensor& labels, const Tensor&
   hip_check(mk::launch_ivf_pack(a, stream()), "ivf_pack");
 }
 
+void ivf_repack(const Tensor& pack_old, const Tensor& cn_old, const Tensor& offsets_old, const Tensor& toff_old,
+                const Tensor& rpos_old, const Tensor& order, const Tensor& offsets, const Tensor& toff,
+                const Tensor& pack, const Tensor& cn, int64_t D, int64_t dpad) {
+  const int dt = dtype_of(pack);
+  const int64_t K = offsets.numel() - 1, n = order.numel(), n_old = rpos_old.numel();
+  TORCH_CHECK(K >= 1 && offsets_old.numel() == K + 1, "mikmeans: ivf_repack offsets must both be [K + 1]");
+  TORCH_CHECK(dpad > 0 && dpad % (4 * vec_of(dt)) == 0,
+              "mikmeans: dpad must be whole 16-B pieces for the four lane groups");
+  TORCH_CHECK(D >= 1 && D <= dpad, "mikmeans: D exceeds dpad");
+  TORCH_CHECK(n_old <= n, "mikmeans: ivf_repack takes no more old ids than ids");
+  check_i64(offsets_old, "offsets_old", K + 1);
+  check_i64(toff_old, "toff_old", K + 1);
+  check_i64(rpos_old, "rpos_old", n_old);
+  check_i64(order, "order", n);
+  check_i64(offsets, "offsets", K + 1);
+  check_i64(toff, "toff", K + 1);
+  // every list padded to whole tiles takes at most (n + 15 K) / 16 tiles
+  check_pack(pack, cn, pack, (n + 15 * K) / 16 * 16, dpad, pack.numel() / dpad);
+  check_pack(pack_old, cn_old, pack, 0, dpad, pack_old.numel() / dpad);
+  TORCH_CHECK(pack.numel() % (16 * dpad) == 0 && pack_old.numel() % (16 * dpad) == 0,
+              "mikmeans: pack must be whole 16-row tiles of dpad columns");
+  TORCH_CHECK(pack.data_ptr() != pack_old.data_ptr() || pack.numel() == 0,
+              "mikmeans: ivf_repack is out of place: the new pack must be a buffer of its own");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pack.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(pack_old.data_ptr()) % 16 == 0,
+              "mikmeans: packs must be 16-B aligned");
+  const int dev = pack.get_device();
+  for (const Tensor* t : {&pack_old, &cn_old, &offsets_old, &toff_old, &rpos_old, &order, &offsets, &toff, &cn})
+    TORCH_CHECK(t->get_device() == dev, "mikmeans: ivf_repack tensors must share a device");
+  mk::IvfRepackArgs a;
+  a.pack_old = pack_old.data_ptr(); a.cn_old = cn_old.data_ptr<float>(); a.rows_old = pack_old.numel() / dpad;
+  a.offsets_old = offsets_old.data_ptr<int64_t>(); a.toff_old = toff_old.data_ptr<int64_t>();
+  a.rpos_old = rpos_old.data_ptr<int64_t>(); a.n_old = n_old;
+  a.order = order.data_ptr<int64_t>(); a.offsets = offsets.data_ptr<int64_t>(); a.toff = toff.data_ptr<int64_t>();
+  a.n = n; a.K = (int)K; a.D = (int)D;
+  a.dtype = dt; a.dpad = (int)dpad; a.pack = pack.data_ptr(); a.cn = cn.data_ptr<float>();
+  a.rows_new = pack.numel() / dpad;
+  hip_check(mk::launch_ivf_repack(a, stream()), "ivf_repack");
+}
+
 void ivf_scan(const Tensor& Q, const Tensor& qn, const Tensor& pack, const Tensor& cn, const Tensor& offsets,
               const Tensor& toff, const Tensor& order, const Tensor& porder, const Tensor& poff, const Tensor& icum,
               int64_t nprobe, int64_t dpad, int64_t P, int64_t max_items, const Tensor& out) {
@@ -1077,6 +1117,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ivf_pack", &ivf_pack, "a block of the index's rows into the fragment-packed row pack, list after list",
         py::arg("X"), py::arg("row0"), py::arg("labels"), py::arg("rpos"), py::arg("offsets"), py::arg("toff"),
         py::arg("pack"), py::arg("cn"), py::arg("dpad"));
+  m.def("ivf_repack", &ivf_repack,
+        "the rows that stay in an updated index, copied from the old fragment-packed row pack into the new one",
+        py::arg("pack_old"), py::arg("cn_old"), py::arg("offsets_old"), py::arg("toff_old"), py::arg("rpos_old"),
+        py::arg("order"), py::arg("offsets"), py::arg("toff"), py::arg("pack"), py::arg("cn"), py::arg("D"),
+        py::arg("dpad"));
   m.def("ivf_scan", &ivf_scan, "the m nearest rows of every (query, probed list) pair as (d2 bits << 32 | row) keys",
         py::arg("Q"), py::arg("qn"), py::arg("pack"), py::arg("cn"), py::arg("offsets"), py::arg("toff"),
         py::arg("order"), py::arg("porder"), py::arg("poff"), py::arg("icum"), py::arg("nprobe"), py::arg("dpad"),

@@ -17,7 +17,9 @@
 //    the fragment-packed layout of kernels.h with their cn -- bit for bit what the centre pack
 //    (csrc/finalize.hip, pack-only) makes of the same rows: both run pack_elem (pack.h) over the
 //    same features per lane and sum the eight lanes by the same butterfly.  X is read in its own
-//    dtype.
+//    dtype.  An index that gains or loses rows is not packed again: the repack copies the rows
+//    that stay from the old pack into a new one under the new offsets, bit for bit, and only the
+//    rows new to the index go through the row pack.
 // 3. Scan: a wave's work item is (list, block of up to 16 P pairs probing it), the items ordered by
 //    list so that neighbouring waves walk the same tiles.  The wave finds its item by a binary
 //    search of the per-list item counts' cumulative sum (the grid is launched at its upper bound,
@@ -207,6 +209,70 @@ hipError_t launch_ivf_pack(const IvfPackArgs& a, hipStream_t s) {
   const unsigned nb = (unsigned)((a.nb + 31) / 32);
   if (a.dtype == DT_BF16) hipLaunchKernelGGL(ivf_pack_kernel<uint16_t>, dim3(nb), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(ivf_pack_kernel<float>, dim3(nb), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ---- 2b. repack ----------------------------------------------------------------------------
+// The rows that stay, from an old pack into a new one (kernels.h IvfRepackArgs): a wave takes one
+// destination tile, lane r + 16 g the 16-byte pieces of lane group g of the tile's row r, so every
+// store instruction of the wave writes 1 KiB in packed order and the sixteen rows of a source tile
+// are read in 256-byte runs.  The wave finds its list by a binary search of the new tile offsets
+// (the grid is launched over the allocation; waves past toff[K] exit), the lane its row's id in
+// the new order and, through the id's old position, its old packed row.  Bits are copied, both
+// dtypes alike (a piece is 16 bytes); pad rows and the rows new to the index are not written.
+// Every destination piece has one writer and nothing written is read: no atomics, no LDS, no
+// barrier.
+constexpr int RP_NW = 4;   // waves (destination tiles) of a workgroup
+
+__global__ __launch_bounds__(RP_NW * 64) void ivf_repack_kernel(IvfRepackArgs a, int nq) {
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 15, g = lane >> 4;
+  const int64_t t = (int64_t)blockIdx.x * RP_NW + wid;
+  if (t >= a.toff[a.K] || (t + 1) * 16 > a.rows_new) return;   // (wave-uniform)
+  int lo = 0, hi = a.K;   // the list k with toff[k] <= t < toff[k + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.toff[mid] <= t) lo = mid;
+    else hi = mid;
+  }
+  const int k = lo;
+  const int64_t p = (t - a.toff[k]) * 16 + r;
+  const int64_t o0 = a.offsets[k];
+  int64_t src = -1;
+  if (p < a.offsets[k + 1] - o0 && o0 + p < a.n) {
+    const int64_t id = a.order[o0 + p];
+    if (id >= 0 && id < a.n_old) {
+      const int64_t po = a.rpos_old[id], b0 = a.offsets_old[k];
+      if (po >= b0 && po < a.offsets_old[k + 1]) {
+        const int64_t s = a.toff_old[k] * 16 + (po - b0);
+        if (s >= 0 && s < a.rows_old) src = s;
+      }
+    }
+  }
+  if (src < 0) return;
+  const u32x4* from = (const u32x4*)a.pack_old + ((src >> 4) * nq * 64 + (src & 15) + 16 * g);
+  u32x4* to = (u32x4*)a.pack + (t * nq * 64 + lane);
+  int q = 0;
+  for (; q + 4 <= nq; q += 4) {
+    const u32x4 v0 = from[(q + 0) * 64], v1 = from[(q + 1) * 64], v2 = from[(q + 2) * 64], v3 = from[(q + 3) * 64];
+    to[(q + 0) * 64] = v0;
+    to[(q + 1) * 64] = v1;
+    to[(q + 2) * 64] = v2;
+    to[(q + 3) * 64] = v3;
+  }
+  for (; q < nq; ++q) to[q * 64] = from[q * 64];
+  if (g == 0) a.cn[t * 16 + r] = a.cn_old[src];
+}
+
+hipError_t launch_ivf_repack(const IvfRepackArgs& a, hipStream_t s) {
+  if (a.n <= 0 || a.n_old <= 0 || a.rows_new <= 0 || a.rows_old <= 0) return hipSuccess;
+  if (a.D > a.dpad || a.K < 1) return hipErrorInvalidValue;
+  const int piece = a.dtype == DT_BF16 ? 8 : 4;   // elements of a 16-byte piece
+  if (a.dpad % (4 * piece) != 0 || a.rows_new % 16 != 0 || a.rows_old % 16 != 0) return hipErrorInvalidValue;
+  const int64_t nb = (a.rows_new / 16 + RP_NW - 1) / RP_NW;
+  if (nb > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ivf_repack_kernel, dim3((unsigned)nb), dim3(RP_NW * 64), 0, s, a, a.dpad / (4 * piece));
   return hipGetLastError();
 }
 

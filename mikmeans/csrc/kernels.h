@@ -153,6 +153,28 @@ struct IvfPackArgs {
   int dtype; int dpad; void* pack; float* cn;
 };
 hipError_t launch_ivf_pack(const IvfPackArgs& a, hipStream_t s);
+// Repack (an index updated in place of a rebuild): the rows that stay move from an old
+// (pack, cn) to a new one under new offsets / toff, their bits copied as stored.  The row at
+// position p of new list k has the id order[offsets[k] + p]; an id below n_old is an old row and
+// comes from old packed row 16 toff_old[k] + rpos_old[id] - offsets_old[k] (rpos_old [n_old]: every
+// id's position in the old order, -1 for an id in no list; an id whose old position lies outside
+// list k is skipped), an id from n_old on is a new row and is left to launch_ivf_pack.  Out of
+// place: the new pack / cn are buffers of their own, filled with zeros / PAD_SCORE by the caller,
+// and hold rows_new packed rows (whole tiles); the old ones hold rows_old.
+struct IvfRepackArgs {
+  const void* pack_old; const float* cn_old; int64_t rows_old;
+  const int64_t* offsets_old;   // [K + 1]
+  const int64_t* toff_old;      // [K + 1]
+  const int64_t* rpos_old;      // [n_old]
+  int64_t n_old;
+  const int64_t* order;         // [n] the new order
+  const int64_t* offsets;       // [K + 1]
+  const int64_t* toff;          // [K + 1]
+  int64_t n;                    // ids handed out (the length of order)
+  int K; int D;
+  int dtype; int dpad; void* pack; float* cn; int64_t rows_new;
+};
+hipError_t launch_ivf_repack(const IvfRepackArgs& a, hipStream_t s);
 // Scan: for every (query, probe) pair -- pair id = query * nprobe + probe, grouped by probed list
 // (porder / poff: launch_partition of the pairs' lists) -- the m smallest keys
 // (d2 bits << 32 | row) over the rows of the pair's list, ascending, into out[pair id][0..m);

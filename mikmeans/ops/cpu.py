@@ -316,6 +316,23 @@ def index_pack(X: torch.Tensor, row0: int, labels: torch.Tensor, rpos: torch.Ten
     cn[dst] = (xf * xf).sum(1)
 
 
+def index_repack(rows_old: torch.Tensor, cn_old: torch.Tensor, offsets_old: torch.Tensor, toff_old: torch.Tensor,
+                 rpos_old: torch.Tensor, labels: torch.Tensor, rpos: torch.Tensor, offsets: torch.Tensor,
+                 toff: torch.Tensor, rows_out: torch.Tensor, cn: torch.Tensor) -> None:
+    """The rows that stay in an updated index, from its old natural-layout row store into the new
+    one (csrc/ivf.hip's repack without the fragment layout): every id below ``rpos_old.numel()``
+    with a list in ``labels`` moves from ``16 toff_old[k] + rpos_old[id] - offsets_old[k]`` to
+    ``16 toff[k] + rpos[id] - offsets[k]``, its row and its ``cn`` as stored."""
+    n_old = rpos_old.numel()
+    lab = labels[:n_old].to(torch.int64)
+    ids = ((lab >= 0) & (rpos_old >= 0)).nonzero().flatten()
+    k = lab[ids]
+    src = toff_old[k] * 16 + rpos_old[ids] - offsets_old[k]
+    dst = toff[k] * 16 + rpos[ids] - offsets[k]
+    rows_out[dst] = rows_old[src]
+    cn[dst] = cn_old[src]
+
+
 def index_search(index, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: int) -> torch.Tensor:
     """Sorted search keys int64 [nq, m] (``d2 bits << 32 | row``, ``IVF_EMPTY_KEY`` padded) over
     the lists of every query's ``nprobe`` nearest centres (:func:`topk`'s indices).  ``d2`` is

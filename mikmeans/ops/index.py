@@ -3,6 +3,8 @@
 * :func:`partition`     rows grouped by label on the device (csrc/ivf.hip: count, scan, scatter)
 * :func:`index_build`   every row's list (:func:`mikmeans.ops.topk` with m = 1), the partition and the
   rows packed list after list as if they were centres
+* :func:`index_add` / :func:`index_remove`  a new index with rows added or taken out: only the new
+  rows meet the centres, the rows that stay are copied from the old pack (csrc/ivf.hip: the repack)
 * :func:`index_search`  the ``nprobe`` nearest centres of every query, the scan of their lists and
   the per-query merge: sorted ``(d2 bits << 32 | row)`` keys
 * :func:`index_range`   every row of those lists within a radius of the query (csrc/range.hip: a count
@@ -21,7 +23,7 @@ from . import TOPK_NATIVE_MAX, cpu, pad_columns, row_sqnorm, topk, topk_blocks
 from .native import dpad_for, dtype_code, require
 
 __all__ = ["PARTITION_MAX_K", "IVF_EMPTY_KEY", "INDEX_MAX_M", "INDEX_SCAN_KEYS", "partition", "RowIndex",
-           "index_tiles", "index_build", "index_search", "index_range", "index_decode"]
+           "index_tiles", "index_build", "index_add", "index_remove", "index_search", "index_range", "index_decode"]
 
 PARTITION_MAX_K = cpu.PARTITION_MAX_K   # csrc/kernels.h (the extension exports the same number)
 IVF_EMPTY_KEY = cpu.IVF_EMPTY_KEY       # a result slot without a row: behind every key
@@ -67,7 +69,8 @@ def index_tiles(n: int, K: int) -> int:
 class RowIndex:
     """The tensors of one index (all on one device):
 
-    ``pack`` the rows, list after list and each list padded to whole 16-row tiles (fragment-packed
+    ``n`` the ids handed out so far (the rows of the build and every row added since, whether in a
+    list or not; fewer than 2^32), ``pack`` the rows, list after list and each list padded to whole 16-row tiles (fragment-packed
     as :func:`mikmeans.ops.pack_centers` packs centres where ``native``, ``[16 tiles, cols]`` natural
     rows otherwise), ``cn`` their squared norms, ``order`` (int64 [n], tail -1) the row ids list after
     list, ``offsets`` / ``tile_offsets`` (int64 [K + 1]) where each list starts in ``order`` / in tiles."""
@@ -125,6 +128,99 @@ def index_build(X, centers: torch.Tensor, *, pack=None, block_rows: int | None =
         else:
             cpu.index_pack(Xt, s, labels, rpos, offsets, toff, rpack.view(tiles * 16, cols), cn)
     return RowIndex(n, K, D, dtype, bool(dpad), cols, rpack, cn, order, offsets, toff)
+
+
+def _id_lists(index: RowIndex):
+    """``(labels int32 [n], rpos int64 [n])`` of an index: every id's list and its position in
+    ``order``, -1 for an id in no list -- ``rpos[order[i]] = i`` and the bucket of ``i`` in
+    ``offsets`` -- on the index's device, without a host read."""
+    n, dev = index.n, index.order.device
+    pos = torch.arange(n, dtype=torch.int64, device=dev)
+    held = index.order >= 0                                   # (order's tail is -1)
+    at = torch.where(held, index.order, n)                    # the tail writes slot n, which is dropped
+    rpos = torch.full((n + 1,), -1, dtype=torch.int64, device=dev)
+    rpos[at] = torch.where(held, pos, -1)
+    labels = torch.full((n + 1,), -1, dtype=torch.int32, device=dev)
+    labels[at] = torch.where(held, torch.bucketize(pos, index.offsets[1:], right=True), -1).to(torch.int32)
+    return labels[:n], rpos[:n]
+
+
+def _update(index: RowIndex, labels: torch.Tensor, rpos_old: torch.Tensor, blocks=None) -> RowIndex:
+    """The index whose ids have the lists ``labels`` (int32 [n], the ids of ``index`` first): the
+    partition, fresh buffers, the rows of ``index`` that keep a list copied from its pack (they
+    keep their list: only -1 may replace a label) and the rows of ``blocks`` -- ``(start, rows,
+    centre pack)`` with ``start`` counted from ``index.n`` -- packed behind them."""
+    n, K, dev = labels.numel(), index.K, labels.device
+    order, offsets, rpos = partition(labels, K, want_pos=True)
+    sizes = offsets[1:] - offsets[:-1]
+    toff = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    toff[1:] = torch.cumsum((sizes + 15) // 16, 0)
+    cols, tiles = index.cols, index_tiles(n, K)
+    rpack = torch.zeros(tiles * 16 * cols, dtype=index.dtype, device=dev)
+    cn = torch.full((tiles * 16,), cpu.PAD_SCORE, dtype=torch.float32, device=dev)
+    if index.native:
+        require().ivf_repack(index.pack, index.cn, index.offsets, index.tile_offsets, rpos_old, order, offsets, toff,
+                             rpack, cn, index.D, cols)
+    else:
+        cpu.index_repack(index.pack.view(-1, cols), index.cn, index.offsets, index.tile_offsets, rpos_old, labels, rpos,
+                         offsets, toff, rpack.view(tiles * 16, cols), cn)
+    for s, Xt, _ in (blocks() if blocks is not None else ()):
+        if index.native:
+            require().ivf_pack(pad_columns(Xt), index.n + s, labels, rpos, offsets, toff, rpack, cn, cols)
+        else:
+            cpu.index_pack(Xt, index.n + s, labels, rpos, offsets, toff, rpack.view(tiles * 16, cols), cn)
+    return RowIndex(n, K, index.D, index.dtype, index.native, cols, rpack, cn, order, offsets, toff)
+
+
+def index_add(index: RowIndex, X, centers: torch.Tensor, *, pack=None, block_rows: int | None = None, blocks=None,
+              n: int | None = None) -> RowIndex:
+    """``index`` with the rows of ``X`` added: a new :class:`RowIndex`, equal tensor for tensor to
+    :func:`index_build` over the old rows followed by the new ones (where no row was removed).  The
+    new rows take the ids ``index.n + i``; a row's list comes from the rule of the build (a row
+    whose nearest distance is NaN or infinite takes an id and is in no list), and within a list the
+    old rows come first, in their old order, then the new rows ascending.  Only the new rows meet
+    the centres and the row pack; the old rows are copied from the old pack into the new one, bits
+    as stored (csrc/ivf.hip: the repack).  ``blocks`` / ``n`` / ``block_rows``: as in
+    :func:`index_build`, over the new rows alone."""
+    if blocks is None:
+        n, blocks = X.shape[0], (lambda: [(0, X, pack)])
+    n0, n1, K = index.n, int(n), index.K
+    if int(centers.shape[0]) != K:
+        raise ValueError(f"the index has {K} lists, the centres are {int(centers.shape[0])}")
+    if n0 + n1 >= 1 << 32:
+        raise ValueError(f"an index takes fewer than 2^32 ids, got {n0} + {n1}")
+    dev = index.order.device
+    labels = torch.empty(n0 + n1, dtype=torch.int32, device=dev)
+    labels[:n0], rpos_old = _id_lists(index)
+    for s, Xt, pk in blocks():
+        Xp = pad_columns(Xt) if Xt.is_cuda else Xt
+        if Xp.dim() != 2 or (Xp.shape[1], Xp.dtype, Xp.device) != (index.D, index.dtype, dev):
+            raise ValueError(f"the index holds rows of {index.D} {index.dtype} features on {dev}, got "
+                             f"{tuple(Xp.shape)} {Xp.dtype} on {Xp.device}")
+        for s2, idx, d2 in topk_blocks(Xp, centers, 1, pack=pk, block_rows=block_rows):
+            a = n0 + s + s2
+            labels[a : a + idx.shape[0]] = torch.where(torch.isfinite(d2[:, 0]), idx[:, 0], -1)
+    return _update(index, labels, rpos_old, blocks)
+
+
+def index_remove(index: RowIndex, ids: torch.Tensor):
+    """``index`` without the rows ``ids`` (int64 local row ids, in any order): ``(RowIndex, removed)``,
+    ``removed`` an int64 0-d tensor on the index's device, the rows that left a list.  Duplicates,
+    ids out of range, ids in no list and ids removed before are ignored.  The rows that stay keep
+    their ids and their order, the lists close up and ``n`` stays (an id is never handed out
+    twice): the result equals :func:`index_build` over the rows that stay, ``order`` mapped back to
+    the old ids.  The rows are copied from the old pack, bits as stored; no host read is made."""
+    ids = torch.as_tensor(ids)
+    if ids.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+        raise ValueError(f"remove takes integer row ids, got {ids.dtype}")
+    n, dev = index.n, index.order.device
+    ids = ids.reshape(-1).to(device=dev, dtype=torch.int64)
+    labels, rpos_old = _id_lists(index)
+    named = torch.zeros(n + 1, dtype=torch.bool, device=dev)
+    named[torch.where((ids >= 0) & (ids < n), ids, n)] = True   # ids out of range name slot n, which is dropped
+    gone = named[:n] & (labels >= 0)
+    removed = gone.sum()
+    return _update(index, torch.where(gone, -1, labels), rpos_old), removed
 
 
 def _scan(index: RowIndex, Qp: torch.Tensor, probes: torch.Tensor, m: int) -> torch.Tensor:

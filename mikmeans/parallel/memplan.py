@@ -479,6 +479,28 @@ def plan_index(n: int, D: int, K: int, dtype="bfloat16", *, block_rows: int | No
     return MemoryPlan("index", n, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
 
 
+def plan_index_update(n_old: int, n_total: int, D: int, K: int, dtype="bfloat16", *,
+                      block_rows: int | None = None) -> MemoryPlan:
+    """An index of ``n_old`` ids updated to ``n_total`` (ops.index_add / ops.index_remove, which
+    keeps ``n_total = n_old``): the old index and the new one, both alive while the rows are copied
+    across, and the update's scratch -- every id's list and position in the new order, the old ids'
+    lists and positions, one block of top-1 output over the new rows and the partition's count
+    cells."""
+    es = esize_of(dtype)
+    Dp = padded_cols(D, es)
+    cols = dpad_for(Dp, es) or Dp
+    p = {}
+    for tag, n in (("old_", n_old), ("", n_total)):
+        rows = index_tiles(n, K) * 16
+        p.update({tag + "row_pack": _r(rows * cols * es), tag + "cn": _r(rows * 4), tag + "order": _r(n * 8),
+                  tag + "offsets": _r((K + 1) * 8), tag + "tile_offsets": _r((K + 1) * 8)})
+    B = min(n_total - n_old, int(block_rows) if block_rows else TOPK_BLOCK_ROWS)
+    tr = {"update": {"labels": _r(n_total * 4), "row_pos": _r(n_total * 8), "old_labels": _r(n_old * 4),
+                     "old_row_pos": _r(n_old * 8), "top1_idx": _r(B * 4), "top1_d2": _r(B * 4), "top1_xn": _r(B * 4),
+                     "top1_labels": _r(B * 4), "partition_cells": _r(K * partition_blocks(n_total, K) * 8)}}
+    return MemoryPlan("index-update", n_total, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
+
+
 # ------------------------------------------------------------------------ budget
 def hbm_budget(device=None) -> int:
     """Bytes a fit on ``device`` may allocate: ``MIKMEANS_HBM_BYTES`` when set, else the free
