@@ -458,30 +458,29 @@ class ClusterIndex:
         shards.  Queries with non-finite coordinates give unspecified results.  numpy in, numpy
         out; host queries bound for a GPU index go through in blocks."""
         mdl = self._model
-        c = mdl.cluster_centers_
-        K = int(c.shape[0])
-        m, nprobe = int(m), int(nprobe)
+        m = int(m)
         if not 1 <= m <= ops.INDEX_MAX_M:
             raise ValueError(f"search needs 1 <= m <= {ops.INDEX_MAX_M}, got m = {m}")
-        if not 1 <= nprobe <= K:
-            raise ValueError(f"search needs 1 <= nprobe <= n_clusters ({K}), got nprobe = {nprobe}")
-        if getattr(Q, "ndim", 2) != 2:
-            raise ValueError(f"Q must be 2-D [n_queries, n_features], got shape {tuple(Q.shape)}")
+        c, nprobe = self._probe_args("search", Q, nprobe)
         (keys,), was_numpy = mdl._row_blocks(
             Q, lambda Qt, pk: (ops.index_search(self._index, Qt, c, m, nprobe, pack=pk),))
         rows, d2 = _merge_search_keys(keys, self._comm, self.row_start)
         d = d2 if squared else d2.sqrt()
         return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
 
-    def _range_args(self, Q, radius, nprobe, squared):
-        """The checked arguments of a range search: ``(centres, nprobe, r2 float32 [nq] on the CPU)``."""
+    def _probe_args(self, what, Q, nprobe):
+        """``(centres, nprobe)`` of a ``what`` ("search" / "range_search") over 2-D queries, checked."""
         c = self._model.cluster_centers_
-        K = int(c.shape[0])
-        nprobe = int(nprobe)
+        K, nprobe = int(c.shape[0]), int(nprobe)
         if not 1 <= nprobe <= K:
-            raise ValueError(f"range_search needs 1 <= nprobe <= n_clusters ({K}), got nprobe = {nprobe}")
+            raise ValueError(f"{what} needs 1 <= nprobe <= n_clusters ({K}), got nprobe = {nprobe}")
         if getattr(Q, "ndim", 2) != 2:
             raise ValueError(f"Q must be 2-D [n_queries, n_features], got shape {tuple(Q.shape)}")
+        return c, nprobe
+
+    def _range_args(self, Q, radius, nprobe, squared):
+        """The checked arguments of a range search: ``(centres, nprobe, r2 float32 [nq] on the CPU)``."""
+        c, nprobe = self._probe_args("range_search", Q, nprobe)
         nq = int(Q.shape[0])
         r = (radius.detach().cpu() if torch.is_tensor(radius) else torch.as_tensor(np.asarray(radius, dtype=np.float64)))
         if r.dim() > 1 or (r.dim() == 1 and r.shape[0] != nq):

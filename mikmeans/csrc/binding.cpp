@@ -80,6 +80,14 @@ void check_pack(const Tensor& pack, const Tensor& cn, const Tensor& X, int64_t r
   TORCH_CHECK(pack.numel() >= rows * dpad, "mikmeans: pack too small (", pack.numel(), " < ", rows, " x ", dpad, ")");
   check_f32(cn, "cn", cn_min);
 }
+// An index's row pack (pack in the dtype of `like`, cn): whole 16-row tiles of dpad columns, and
+// room for n ids in K lists -- every list padded to whole tiles takes at most (n + 15 K) / 16 tiles
+// (n = K = 0: any length).
+void check_row_pack(const Tensor& pack, const Tensor& cn, const Tensor& like, int64_t dpad, int64_t n = 0,
+                    int64_t K = 0) {
+  check_pack(pack, cn, like, (n + 15 * K) / 16 * 16, dpad, pack.numel() / dpad);
+  TORCH_CHECK(pack.numel() % (16 * dpad) == 0, "mikmeans: pack must be whole 16-row tiles of dpad columns");
+}
 template <typename T>
 T* opt_ptr(const c10::optional<Tensor>& t) {
   return t.has_value() && t->defined() ? reinterpret_cast<T*>(t->data_ptr()) : nullptr;
@@ -262,9 +270,7 @@ void ivf_pack(const Tensor& X, int64_t row0, const Tensor& labels, const Tensor&
   check_i64(rpos, "rpos", n);
   check_i64(offsets, "offsets", K + 1);
   check_i64(toff, "toff", K + 1);
-  // every list padded to whole tiles takes at most (n + 15 K) / 16 tiles
-  check_pack(pack, cn, X, (n + 15 * K) / 16 * 16, dpad, pack.numel() / dpad);
-  TORCH_CHECK(pack.numel() % (16 * dpad) == 0, "mikmeans: pack must be whole 16-row tiles of dpad columns");
+  check_row_pack(pack, cn, X, dpad, n, K);
   mk::IvfPackArgs a;
   a.X = X.data_ptr(); a.nb = nb; a.D = (int)X.size(1); a.ldx = ldx; a.row0 = row0;
   a.labels = labels.data_ptr<int32_t>(); a.rpos = rpos.data_ptr<int64_t>();
@@ -289,11 +295,8 @@ void ivf_repack(const Tensor& pack_old, const Tensor& cn_old, const Tensor& offs
   check_i64(order, "order", n);
   check_i64(offsets, "offsets", K + 1);
   check_i64(toff, "toff", K + 1);
-  // every list padded to whole tiles takes at most (n + 15 K) / 16 tiles
-  check_pack(pack, cn, pack, (n + 15 * K) / 16 * 16, dpad, pack.numel() / dpad);
-  check_pack(pack_old, cn_old, pack, 0, dpad, pack_old.numel() / dpad);
-  TORCH_CHECK(pack.numel() % (16 * dpad) == 0 && pack_old.numel() % (16 * dpad) == 0,
-              "mikmeans: pack must be whole 16-row tiles of dpad columns");
+  check_row_pack(pack, cn, pack, dpad, n, K);
+  check_row_pack(pack_old, cn_old, pack, dpad);
   TORCH_CHECK(pack.data_ptr() != pack_old.data_ptr() || pack.numel() == 0,
               "mikmeans: ivf_repack is out of place: the new pack must be a buffer of its own");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(pack.data_ptr()) % 16 == 0 &&
@@ -313,37 +316,54 @@ void ivf_repack(const Tensor& pack_old, const Tensor& cn_old, const Tensor& offs
   hip_check(mk::launch_ivf_repack(a, stream()), "ivf_repack");
 }
 
-void ivf_scan(const Tensor& Q, const Tensor& qn, const Tensor& pack, const Tensor& cn, const Tensor& offsets,
-              const Tensor& toff, const Tensor& order, const Tensor& porder, const Tensor& poff, const Tensor& icum,
-              int64_t nprobe, int64_t dpad, int64_t P, int64_t max_items, const Tensor& out) {
+// A walk over the index's lists (kernels.h IvfWalkArgs) as ivf_scan and ivf_range take it.
+// `blocks(dt, npairs)` checks the op's own tensors and returns its pair blocks per wave (P is that
+// or 1).  max_items: from the full blocks alone (walk_max_items of no list) to K + 1 above.
+template <typename Blocks>
+mk::IvfWalkArgs check_walk(const char* op, const Tensor& Q, const Tensor& qn, const Tensor& pack, const Tensor& cn,
+                           const Tensor& offsets, const Tensor& toff, const Tensor& order, const Tensor& porder,
+                           const Tensor& poff, const Tensor& icum, int64_t nprobe, int64_t dpad, int64_t P,
+                           int64_t max_items, Blocks blocks) {
   const int dt = dtype_of(Q);
   const int64_t ldq = check_points_dpad(Q, dt, dpad);
   const int64_t nq = Q.size(0), K = offsets.numel() - 1, npairs = nq * nprobe;
-  TORCH_CHECK(K >= 1 && nprobe >= 1 && nprobe <= K, "mikmeans: ivf_scan needs 1 <= nprobe <= K");
+  TORCH_CHECK(K >= 1 && nprobe >= 1 && nprobe <= K, "mikmeans: ", op, " needs 1 <= nprobe <= K");
   check_f32(qn, "qn", nq);
-  check_pack(pack, cn, Q, 0, dpad, pack.numel() / dpad);
-  TORCH_CHECK(pack.numel() % (16 * dpad) == 0, "mikmeans: pack must be whole 16-row tiles of dpad columns");
+  check_row_pack(pack, cn, Q, dpad);
   check_i64(offsets, "offsets", K + 1);
   check_i64(toff, "toff", K + 1);
   check_i64(order, "order", 0);
   check_i64(porder, "porder", npairs);
   check_i64(poff, "poff", K + 1);
   check_i64(icum, "icum", K + 1);
-  TORCH_CHECK(out.dim() == 2 && out.size(0) == npairs, "mikmeans: out must be [nq * nprobe, m]");
-  const int64_t m = out.size(1);
-  TORCH_CHECK(m >= 1 && m <= mk::TOPK_MAX, "mikmeans: ivf_scan needs 1 <= m <= ", mk::TOPK_MAX, ", got m = ", m);
-  check_i64(out, "out", npairs * m);
-  TORCH_CHECK(P == mk::ivf_scan_blocks(dt, (int)dpad, (int)m, npairs) || P == 1, "mikmeans: bad ivf_scan P ", P);
-  TORCH_CHECK(max_items >= npairs / (16 * P) && max_items <= npairs / (16 * P) + K + 1,
-              "mikmeans: bad ivf_scan max_items ", max_items);
+  TORCH_CHECK(P == blocks(dt, npairs) || P == 1, "mikmeans: bad ", op, " P ", P);
+  const int64_t lo = mk::walk_max_items(npairs, 0, (int)P);
+  TORCH_CHECK(max_items >= lo && max_items <= lo + K + 1, "mikmeans: bad ", op, " max_items ", max_items);
+  mk::IvfWalkArgs w;
+  w.Q = Q.data_ptr(); w.D = (int)Q.size(1); w.ldq = ldq; w.qn = qn.data_ptr<float>();
+  w.pack = pack.data_ptr(); w.cn = cn.data_ptr<float>();
+  w.offsets = offsets.data_ptr<int64_t>(); w.toff = toff.data_ptr<int64_t>(); w.order = order.data_ptr<int64_t>();
+  w.porder = porder.data_ptr<int64_t>(); w.poff = poff.data_ptr<int64_t>(); w.icum = icum.data_ptr<int64_t>();
+  w.K = (int)K; w.nprobe = (int)nprobe; w.npairs = npairs; w.max_items = max_items;
+  return w;
+}
+
+void ivf_scan(const Tensor& Q, const Tensor& qn, const Tensor& pack, const Tensor& cn, const Tensor& offsets,
+              const Tensor& toff, const Tensor& order, const Tensor& porder, const Tensor& poff, const Tensor& icum,
+              int64_t nprobe, int64_t dpad, int64_t P, int64_t max_items, const Tensor& out) {
   mk::IvfScanArgs a;
-  a.Q = Q.data_ptr(); a.D = (int)Q.size(1); a.ldq = ldq; a.qn = qn.data_ptr<float>();
-  a.pack = pack.data_ptr(); a.cn = cn.data_ptr<float>();
-  a.offsets = offsets.data_ptr<int64_t>(); a.toff = toff.data_ptr<int64_t>(); a.order = order.data_ptr<int64_t>();
-  a.porder = porder.data_ptr<int64_t>(); a.poff = poff.data_ptr<int64_t>(); a.icum = icum.data_ptr<int64_t>();
-  a.K = (int)K; a.nprobe = (int)nprobe; a.m = (int)m; a.npairs = npairs; a.max_items = max_items;
+  a.w = check_walk("ivf_scan", Q, qn, pack, cn, offsets, toff, order, porder, poff, icum, nprobe, dpad, P, max_items,
+                   [&](int dt, int64_t npairs) {
+                     TORCH_CHECK(out.dim() == 2 && out.size(0) == npairs, "mikmeans: out must be [nq * nprobe, m]");
+                     const int64_t m = out.size(1);
+                     TORCH_CHECK(m >= 1 && m <= mk::TOPK_MAX, "mikmeans: ivf_scan needs 1 <= m <= ", mk::TOPK_MAX,
+                                 ", got m = ", m);
+                     check_i64(out, "out", npairs * m);
+                     return mk::ivf_scan_blocks(dt, (int)dpad, (int)m, npairs);
+                   });
+  a.m = (int)out.size(1);
   a.out = reinterpret_cast<long long*>(out.data_ptr<int64_t>());
-  hip_check(mk::launch_ivf_scan(dt, (int)dpad, (int)P, a, stream()), "ivf_scan");
+  hip_check(mk::launch_ivf_scan(dtype_of(Q), (int)dpad, (int)P, a, stream()), "ivf_scan");
 }
 
 // Range search (csrc/range.hip): the count pass (counts alone) or the fill pass (base and keys too)
@@ -351,41 +371,26 @@ void ivf_range(const Tensor& Q, const Tensor& qn, const Tensor& r2, const Tensor
                const Tensor& offsets, const Tensor& toff, const Tensor& order, const Tensor& porder, const Tensor& poff,
                const Tensor& icum, int64_t nprobe, int64_t dpad, int64_t P, int64_t max_items, const Tensor& counts,
                const c10::optional<Tensor>& base, const c10::optional<Tensor>& keys) {
-  const int dt = dtype_of(Q);
-  const int64_t ldq = check_points_dpad(Q, dt, dpad);
-  const int64_t nq = Q.size(0), K = offsets.numel() - 1, npairs = nq * nprobe;
-  TORCH_CHECK(K >= 1 && nprobe >= 1 && nprobe <= K, "mikmeans: ivf_range needs 1 <= nprobe <= K");
-  check_f32(qn, "qn", nq);
-  check_f32(r2, "r2", nq);
-  check_pack(pack, cn, Q, 0, dpad, pack.numel() / dpad);
-  TORCH_CHECK(pack.numel() % (16 * dpad) == 0, "mikmeans: pack must be whole 16-row tiles of dpad columns");
-  check_i64(offsets, "offsets", K + 1);
-  check_i64(toff, "toff", K + 1);
-  check_i64(order, "order", 0);
-  check_i64(porder, "porder", npairs);
-  check_i64(poff, "poff", K + 1);
-  check_i64(icum, "icum", K + 1);
-  check_i64(counts, "counts", npairs);
   const bool fill = base.has_value() && base->defined();
-  TORCH_CHECK(fill == (keys.has_value() && keys->defined()), "mikmeans: ivf_range's fill pass takes base and keys");
-  if (fill) {
-    check_i64(*base, "base", npairs);
-    check_i64(*keys, "keys", 0);
-  }
-  TORCH_CHECK(P == mk::ivf_range_blocks(dt, (int)dpad, npairs) || P == 1, "mikmeans: bad ivf_range P ", P);
-  TORCH_CHECK(max_items >= npairs / (16 * P) && max_items <= npairs / (16 * P) + K + 1,
-              "mikmeans: bad ivf_range max_items ", max_items);
   mk::IvfRangeArgs a;
-  a.Q = Q.data_ptr(); a.D = (int)Q.size(1); a.ldq = ldq; a.qn = qn.data_ptr<float>(); a.r2 = r2.data_ptr<float>();
-  a.pack = pack.data_ptr(); a.cn = cn.data_ptr<float>();
-  a.offsets = offsets.data_ptr<int64_t>(); a.toff = toff.data_ptr<int64_t>(); a.order = order.data_ptr<int64_t>();
-  a.porder = porder.data_ptr<int64_t>(); a.poff = poff.data_ptr<int64_t>(); a.icum = icum.data_ptr<int64_t>();
-  a.K = (int)K; a.nprobe = (int)nprobe; a.npairs = npairs; a.max_items = max_items;
+  a.w = check_walk("ivf_range", Q, qn, pack, cn, offsets, toff, order, porder, poff, icum, nprobe, dpad, P, max_items,
+                   [&](int dt, int64_t npairs) {
+                     check_f32(r2, "r2", Q.size(0));
+                     check_i64(counts, "counts", npairs);
+                     TORCH_CHECK(fill == (keys.has_value() && keys->defined()),
+                                 "mikmeans: ivf_range's fill pass takes base and keys");
+                     if (fill) {
+                       check_i64(*base, "base", npairs);
+                       check_i64(*keys, "keys", 0);
+                     }
+                     return mk::ivf_range_blocks(dt, (int)dpad, npairs);
+                   });
+  a.r2 = r2.data_ptr<float>();
   a.counts = counts.data_ptr<int64_t>();
   a.base = fill ? base->data_ptr<int64_t>() : nullptr;
   a.keys = fill ? reinterpret_cast<long long*>(keys->data_ptr<int64_t>()) : nullptr;
   a.total = fill ? keys->numel() : 0;
-  hip_check(mk::launch_ivf_range(dt, (int)dpad, (int)P, fill, a, stream()), "ivf_range");
+  hip_check(mk::launch_ivf_range(dtype_of(Q), (int)dpad, (int)P, fill, a, stream()), "ivf_range");
 }
 
 void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {

@@ -20,10 +20,8 @@
 //    dtype.  An index that gains or loses rows is not packed again: the repack copies the rows
 //    that stay from the old pack into a new one under the new offsets, bit for bit, and only the
 //    rows new to the index go through the row pack.
-// 3. Scan: a wave's work item is (list, block of up to 16 P pairs probing it), the items ordered by
-//    list so that neighbouring waves walk the same tiles.  The wave finds its item by a binary
-//    search of the per-list item counts' cumulative sum (the grid is launched at its upper bound,
-//    waves past the total exit), gathers its queries' fragments as topk_kernel holds rows, walks
+// 3. Scan: a wave takes one work item of the walk over the lists (csrc/walk.h: a list and a block
+//    of the pairs probing it), gathers its queries' fragments as topk_kernel holds rows, walks
 //    the list's tiles straight from global memory and keeps the M best (d2 bits, position in
 //    list) per lane with the insertion of topk.h; a query's four lanes merge through LDS and lane
 //    r writes the pair's m keys (d2 bits << 32 | row).  d2 is bitwise the transform kernel's value
@@ -216,7 +214,7 @@ hipError_t launch_ivf_pack(const IvfPackArgs& a, hipStream_t s) {
 // The rows that stay, from an old pack into a new one (kernels.h IvfRepackArgs): a wave takes one
 // destination tile, lane r + 16 g the 16-byte pieces of lane group g of the tile's row r, so every
 // store instruction of the wave writes 1 KiB in packed order and the sixteen rows of a source tile
-// are read in 256-byte runs.  The wave finds its list by a binary search of the new tile offsets
+// are read in 256-byte runs.  The wave finds its list by list_of (walk.h) over the new tile offsets
 // (the grid is launched over the allocation; waves past toff[K] exit), the lane its row's id in
 // the new order and, through the id's old position, its old packed row.  Bits are copied, both
 // dtypes alike (a piece is 16 bytes); pad rows and the rows new to the index are not written.
@@ -230,13 +228,7 @@ __global__ __launch_bounds__(RP_NW * 64) void ivf_repack_kernel(IvfRepackArgs a,
   const int r = lane & 15, g = lane >> 4;
   const int64_t t = (int64_t)blockIdx.x * RP_NW + wid;
   if (t >= a.toff[a.K] || (t + 1) * 16 > a.rows_new) return;   // (wave-uniform)
-  int lo = 0, hi = a.K;   // the list k with toff[k] <= t < toff[k + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.toff[mid] <= t) lo = mid;
-    else hi = mid;
-  }
-  const int k = lo;
+  const int k = list_of(a.toff, a.K, t);
   const int64_t p = (t - a.toff[k]) * 16 + r;
   const int64_t o0 = a.offsets[k];
   int64_t src = -1;
@@ -287,19 +279,8 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_scan_kernel(IvfScanArgs a) 
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int64_t item = (int64_t)blockIdx.x * TK_NW + wid;
-  if (item >= a.icum[a.K]) return;   // (wave-uniform; the kernel has no workgroup barrier)
-  int lo = 0, hi = a.K;              // the list l with icum[l] <= item < icum[l + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.icum[mid] <= item) lo = mid;
-    else hi = mid;
-  }
-  const int l = lo;
-  const int64_t p0 = a.poff[l] + (item - a.icum[l]) * (P * 16);
-  const int64_t pleft = a.poff[l + 1] - p0;
-  const int np = (int)(pleft < P * 16 ? pleft : P * 16);   // the item's pairs, >= 1
-  const int64_t o0 = a.offsets[l];
-  const int nl = (int)(a.offsets[l + 1] - o0);             // the list's rows
+  if (item >= a.w.icum[a.w.K]) return;   // (wave-uniform; the kernel has no workgroup barrier)
+  const WalkItem it = walk_item<P * 16>(a.w.icum, a.w.poff, a.w.offsets, a.w.K, item);
   u32x4 xr[P][XREG ? NQ : 1];
   const T* xp[P];
   float xn[P];
@@ -307,8 +288,8 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_scan_kernel(IvfScanArgs a) 
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     const int slot = p * 16 + r;
-    pid[p] = a.porder[p0 + (slot < np ? slot : np - 1)];
-    load_row<T, NQ, XREG>(a.Q, a.ldq, pid[p] / a.nprobe, a.qn, g, a.D, xr[p], xp[p], xn[p]);
+    pid[p] = a.w.porder[it.p0 + (slot < it.np ? slot : it.np - 1)];
+    load_row<T, NQ, XREG>(a.w.Q, a.w.ldq, pid[p] / a.w.nprobe, a.w.qn, g, a.w.D, xr[p], xp[p], xn[p]);
   }
   uint32_t bv[P][M];
   int bi[P][M];
@@ -321,12 +302,12 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_scan_kernel(IvfScanArgs a) 
     }
   }
   // the list's tiles; a position past its length is an empty candidate
-  const int64_t t0 = a.toff[l];
-  tk_scan<T, NQ, P, M, XREG>((const T*)a.pack + t0 * (NQ * 64 * V), a.cn + t0 * 16, 0, (nl + 15) / 16, nl, lane, g, xr,
-                             xp, a.D, xn, bv, bi);
+  const int64_t t0 = a.w.toff[it.list];
+  tk_scan<T, NQ, P, M, XREG>((const T*)a.w.pack + t0 * (NQ * 64 * V), a.w.cn + t0 * 16, 0, (it.nl + 15) / 16, it.nl,
+                             lane, g, xr, xp, a.w.D, xn, bv, bi);
   MK_LDS unsigned long long* ws = (MK_LDS unsigned long long*)sm + wid * (M * 64);
-  const int64_t* ord = a.order + o0;
-  tk_merge_rows(ws, lane, np, a.m, bv, bi, [&](int p) {
+  const int64_t* ord = a.w.order + it.o0;
+  tk_merge_rows(ws, lane, it.np, a.m, bv, bi, [&](int p) {
     long long* out = a.out + pid[p] * a.m;
     return [=](int j, unsigned long long best) {
       const uint32_t bits = (uint32_t)(best >> 32);
@@ -337,40 +318,47 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_scan_kernel(IvfScanArgs a) 
   });
 }
 
+// The walk's launch (kernels.h): TK_NW items a workgroup over max_items, the upper bound of icum[K]
+hipError_t ivf_walk_grid(const IvfWalkArgs& w, int dpad, int64_t& nb) {
+  nb = 0;
+  if (w.npairs <= 0 || w.max_items <= 0) return hipSuccess;
+  if (w.K < 1 || w.nprobe < 1 || w.D > dpad) return hipErrorInvalidValue;
+  if ((w.max_items + TK_NW - 1) / TK_NW > 0x7fffffff) return hipErrorInvalidValue;
+  nb = (w.max_items + TK_NW - 1) / TK_NW;
+  return hipSuccess;
+}
+
 template <typename T, int DPAD, int P, int M>
-static hipError_t launch_is_p(const IvfScanArgs& a, hipStream_t s) {
-  const int64_t nb = (a.max_items + TK_NW - 1) / TK_NW;
+static hipError_t launch_is_p(int64_t nb, const IvfScanArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((ivf_scan_kernel<T, DPAD, P, M>), dim3((unsigned)nb), dim3(TK_NW * 64), 0, s, a);
   return hipGetLastError();
 }
 
 template <typename T, int DPAD, int M>
-static hipError_t launch_is_m(int P, const IvfScanArgs& a, hipStream_t s) {
+static hipError_t launch_is_m(int P, int64_t nb, const IvfScanArgs& a, hipStream_t s) {
   constexpr int PF = topk_blocks(DPAD / 4 / Elem<T>::V, M);
-  if (P == 1) return launch_is_p<T, DPAD, 1, M>(a, s);
-  if (P == PF) return launch_is_p<T, DPAD, PF, M>(a, s);
+  if (P == 1) return launch_is_p<T, DPAD, 1, M>(nb, a, s);
+  if (P == PF) return launch_is_p<T, DPAD, PF, M>(nb, a, s);
   return hipErrorInvalidValue;
 }
 
 template <typename T, int DPAD>
-static hipError_t launch_is(int P, const IvfScanArgs& a, hipStream_t s) {
-  return a.m <= 8 ? launch_is_m<T, DPAD, 8>(P, a, s) : launch_is_m<T, DPAD, 32>(P, a, s);
+static hipError_t launch_is(int P, int64_t nb, const IvfScanArgs& a, hipStream_t s) {
+  return a.m <= 8 ? launch_is_m<T, DPAD, 8>(P, nb, a, s) : launch_is_m<T, DPAD, 32>(P, nb, a, s);
 }
 
-// Pair blocks per wave: topk's rule (topk_blocks; one block for a small batch of pairs, so more
-// waves share the work)
+// Pair blocks per wave: topk's rule (topk_blocks, then walk_blocks over the pairs)
 int ivf_scan_blocks(int dtype, int dpad, int m, int64_t npairs) {
   const int nq = dpad / 4 / (dtype == DT_BF16 ? 8 : 4);
-  const int P = topk_blocks(nq, m <= 8 ? 8 : 32);
-  return (P > 1 && npairs < (int64_t)32768 * P) ? 1 : P;
+  return walk_blocks(topk_blocks(nq, m <= 8 ? 8 : 32), npairs);
 }
 
 hipError_t launch_ivf_scan(int dtype, int dpad, int P, const IvfScanArgs& a, hipStream_t s) {
-  if (a.npairs <= 0 || a.max_items <= 0) return hipSuccess;
-  if (a.K < 1 || a.m < 1 || a.m > TOPK_MAX || a.nprobe < 1 || a.D > dpad) return hipErrorInvalidValue;
-  if ((a.max_items + TK_NW - 1) / TK_NW > 0x7fffffff) return hipErrorInvalidValue;
+  int64_t nb;
+  if (const hipError_t e = ivf_walk_grid(a.w, dpad, nb); e != hipSuccess || nb == 0) return e;
+  if (a.m < 1 || a.m > TOPK_MAX) return hipErrorInvalidValue;
   return (hipError_t)for_width(dtype, dpad, [&](auto t, auto w) {
-    return launch_is<typename decltype(t)::type, decltype(w)::value>(P, a, s);
+    return launch_is<typename decltype(t)::type, decltype(w)::value>(P, nb, a, s);
   });
 }
 

@@ -9,6 +9,7 @@
 
 #include "dispatch.h"   // for_width: the (dtype, padded width) switch of every launcher that has one
 #include "fold.h"       // the frame constants of the per-cluster folds (FOLD_*)
+#include "walk.h"       // the work item of a walk over an index's lists, its grid bound, walk_blocks
 
 namespace mk {
 
@@ -175,42 +176,14 @@ struct IvfRepackArgs {
   int dtype; int dpad; void* pack; float* cn; int64_t rows_new;
 };
 hipError_t launch_ivf_repack(const IvfRepackArgs& a, hipStream_t s);
-// Scan: for every (query, probe) pair -- pair id = query * nprobe + probe, grouped by probed list
-// (porder / poff: launch_partition of the pairs' lists) -- the m smallest keys
-// (d2 bits << 32 | row) over the rows of the pair's list, ascending, into out[pair id][0..m);
-// IVF_EMPTY_KEY where the list has fewer than m rows.  d2 is bitwise launch_transform's value of
-// the query against the row packed as a centre.  A wave takes (list, block of up to 16 P pairs):
-// icum [K + 1] = the cumulative sum of ceil(pairs_l / 16 P), max_items an upper bound of icum[K]
-// (the grid; waves past icum[K] exit).  P from ivf_scan_blocks.  1 <= m <= TOPK_MAX.
-constexpr long long IVF_EMPTY_KEY = 0x7fffffffffffffffLL;
-struct IvfScanArgs {
+// A walk over the index's lists (csrc/walk.h), shared by the scan and the range search: the
+// (query, probe) pairs -- pair id = query * nprobe + probe -- grouped by probed list (porder / poff:
+// launch_partition of the pairs' lists).  A wave's work item is (list, block of up to 16 P pairs
+// probing it): icum [K + 1] = the cumulative sum of ceil(pairs_l / 16 P), max_items an upper bound
+// of icum[K] (the grid; waves past icum[K] exit), walk_max_items gives one without a host read.
+struct IvfWalkArgs {
   const void* Q; int D; int64_t ldq;
   const float* qn;           // |q|^2 per query
-  const void* pack; const float* cn;   // the row pack
-  const int64_t* offsets;    // [K + 1] list starts in order
-  const int64_t* toff;       // [K + 1] list starts in tiles
-  const int64_t* order;      // row ids, list after list
-  const int64_t* porder;     // [npairs] pair ids grouped by list
-  const int64_t* poff;       // [K + 1]
-  const int64_t* icum;       // [K + 1]
-  int K; int nprobe; int m;
-  int64_t npairs; int64_t max_items;
-  long long* out;            // [npairs, m]
-};
-int ivf_scan_blocks(int dtype, int dpad, int m, int64_t npairs);
-hipError_t launch_ivf_scan(int dtype, int dpad, int P, const IvfScanArgs& a, hipStream_t s);
-
-// ---- range search through the clusters (csrc/range.hip) -----------------------------------
-// Every row of a pair's list with bits(d2) <= bits(r2[query]), on the scan's work items (pairs
-// grouped by list, icum over ceil(pairs_l / 16 P), P from ivf_range_blocks) and with the scan's
-// d2.  Two launches: the count pass writes counts[pair id] (int64), the fill pass writes pair
-// p's keys (d2 bits << 32 | row) in list order from keys[base[p]] on -- base = the caller's
-// exclusive cumulative sum of counts in pair-id order, total = its end (no key is written at or
-// past it).  r2: one finite non-negative float per query.  Bitwise the same on every launch.
-struct IvfRangeArgs {
-  const void* Q; int D; int64_t ldq;
-  const float* qn;           // |q|^2 per query
-  const float* r2;           // squared radius per query
   const void* pack; const float* cn;   // the row pack
   const int64_t* offsets;    // [K + 1] list starts in order
   const int64_t* toff;       // [K + 1] list starts in tiles
@@ -220,6 +193,33 @@ struct IvfRangeArgs {
   const int64_t* icum;       // [K + 1]
   int K; int nprobe;
   int64_t npairs; int64_t max_items;
+};
+// What launch_ivf_scan / launch_ivf_range check of a walk, and its grid: nb = workgroups, 0 where
+// there is nothing to do (no pairs); hipErrorInvalidValue for arguments no kernel may see.
+hipError_t ivf_walk_grid(const IvfWalkArgs& w, int dpad, int64_t& nb);
+// Scan: for every pair of the walk the m smallest keys (d2 bits << 32 | row) over the rows of the
+// pair's list, ascending, into out[pair id][0..m); IVF_EMPTY_KEY where the list has fewer than m
+// rows.  d2 is bitwise launch_transform's value of the query against the row packed as a centre.
+// P from ivf_scan_blocks.  1 <= m <= TOPK_MAX.
+constexpr long long IVF_EMPTY_KEY = 0x7fffffffffffffffLL;
+struct IvfScanArgs {
+  IvfWalkArgs w;
+  int m;
+  long long* out;            // [npairs, m]
+};
+int ivf_scan_blocks(int dtype, int dpad, int m, int64_t npairs);
+hipError_t launch_ivf_scan(int dtype, int dpad, int P, const IvfScanArgs& a, hipStream_t s);
+
+// ---- range search through the clusters (csrc/range.hip) -----------------------------------
+// Every row of a pair's list with bits(d2) <= bits(r2[query]), on the walk's work items (P from
+// ivf_range_blocks) and with the scan's d2.  Two launches: the count pass writes counts[pair id]
+// (int64), the fill pass writes pair p's keys (d2 bits << 32 | row) in list order from
+// keys[base[p]] on -- base = the caller's exclusive cumulative sum of counts in pair-id order,
+// total = its end (no key is written at or past it).  r2: one finite non-negative float per
+// query.  Bitwise the same on every launch.
+struct IvfRangeArgs {
+  IvfWalkArgs w;
+  const float* r2;           // squared radius per query
   int64_t* counts;           // [npairs] (count pass)
   const int64_t* base;       // [npairs] (fill pass)
   long long* keys;           // [total]  (fill pass)

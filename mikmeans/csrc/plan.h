@@ -12,8 +12,10 @@
 
 #if defined(__HIPCC__) || defined(__HIP__)
 #define MK_HD __host__ __device__
+#define MK_HD_INLINE __host__ __device__ __forceinline__   // a piece of a kernel's body (csrc/walk.h)
 #else
 #define MK_HD
+#define MK_HD_INLINE inline
 #endif
 
 namespace mk {

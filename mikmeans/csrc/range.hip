@@ -2,12 +2,11 @@
 // gfx950: every indexed row within a radius of each query, over the lists of the query's probed
 // centres.
 //
-// The work item, the row pack and the tile step are the scan's (csrc/ivf.hip): a wave takes (list,
-// block of up to 16 P (query, probe) pairs probing it), finds it by the same binary search of the
-// per-list item counts' cumulative sum, holds its queries' fragments as load_row gives them and
-// walks the list's tiles with tile_d2 -- so d2 is bitwise the scan's and the transform kernel's
-// value for (query, row).  What differs is what is kept: no candidate list, so the result has no
-// fixed length and is written in two passes with a host-side cumulative sum between them.
+// The work item (csrc/walk.h), the row pack and the tile step are the scan's (csrc/ivf.hip): a wave
+// holds the queries of its item's pairs as load_row gives them and walks the list's tiles with
+// tile_d2 -- so d2 is bitwise the scan's and the transform kernel's value for (query, row).  What
+// differs is what is kept: no candidate list, so the result has no fixed length and is written in
+// two passes with a host-side cumulative sum between them.
 //
 // 1. Count: a lane counts the tile entries with k < list length and bits(d2) <= bits(r2[query])
 //    (d2 is clamped to +0 .. +inf or the one NaN pattern, r2 is finite and non-negative: the
@@ -48,19 +47,9 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_range_kernel(IvfRangeArgs a
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
   const int64_t item = (int64_t)blockIdx.x * TK_NW + wid;
-  if (item >= a.icum[a.K]) return;   // (wave-uniform; the kernel has no workgroup barrier)
-  int lo = 0, hi = a.K;              // the list l with icum[l] <= item < icum[l + 1]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (a.icum[mid] <= item) lo = mid;
-    else hi = mid;
-  }
-  const int l = lo;
-  const int64_t p0 = a.poff[l] + (item - a.icum[l]) * (P * 16);
-  const int64_t pleft = a.poff[l + 1] - p0;
-  const int np = (int)(pleft < P * 16 ? pleft : P * 16);   // the item's pairs, >= 1
-  const int64_t o0 = a.offsets[l];
-  const int nl = (int)(a.offsets[l + 1] - o0);             // the list's rows
+  if (item >= a.w.icum[a.w.K]) return;   // (wave-uniform; the kernel has no workgroup barrier)
+  const WalkItem it = walk_item<P * 16>(a.w.icum, a.w.poff, a.w.offsets, a.w.K, item);
+  const int nl = it.nl;
   u32x4 xr[P][XREG ? NQ : 1];
   const T* xp[P];
   float xn[P];
@@ -70,22 +59,22 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_range_kernel(IvfRangeArgs a
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     const int slot = p * 16 + r;
-    live[p] = slot < np;
-    pid[p] = a.porder[p0 + (live[p] ? slot : np - 1)];
-    const int64_t q = pid[p] / a.nprobe;
-    load_row<T, NQ, XREG>(a.Q, a.ldq, q, a.qn, g, a.D, xr[p], xp[p], xn[p]);
+    live[p] = slot < it.np;
+    pid[p] = a.w.porder[it.p0 + (live[p] ? slot : it.np - 1)];
+    const int64_t q = pid[p] / a.w.nprobe;
+    load_row<T, NQ, XREG>(a.w.Q, a.w.ldq, q, a.w.qn, g, a.w.D, xr[p], xp[p], xn[p]);
     rb[p] = __float_as_uint(a.r2[q]);
     run[p] = 0u;
     base[p] = FILL ? a.base[pid[p]] : 0;
   }
-  const int64_t t0 = a.toff[l];
-  const T* pack = (const T*)a.pack + t0 * (NQ * 64 * V);
-  const float* cn = a.cn + t0 * 16;
-  const int64_t* ord = a.order + o0;
+  const int64_t t0 = a.w.toff[it.list];
+  const T* pack = (const T*)a.w.pack + t0 * (NQ * 64 * V);
+  const float* cn = a.w.cn + t0 * 16;
+  const int64_t* ord = a.w.order + it.o0;
   const int nt = (nl + 15) / 16;
   for (int t = 0; t < nt; ++t) {
     f32x4 d2[P];
-    tile_d2<T, NQ, P, XREG>(pack, cn, t, lane, g, xr, xp, a.D, xn, d2);
+    tile_d2<T, NQ, P, XREG>(pack, cn, t, lane, g, xr, xp, a.w.D, xn, d2);
     const int k0 = t * 16 + 4 * g;
 #pragma unroll
     for (int p = 0; p < P; ++p) {
@@ -129,35 +118,32 @@ __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_range_kernel(IvfRangeArgs a
 }
 
 template <typename T, int DPAD, int P>
-static hipError_t launch_ir_p(bool fill, const IvfRangeArgs& a, hipStream_t s) {
-  const int64_t nb = (a.max_items + TK_NW - 1) / TK_NW;
+static hipError_t launch_ir_p(bool fill, int64_t nb, const IvfRangeArgs& a, hipStream_t s) {
   if (fill) hipLaunchKernelGGL((ivf_range_kernel<T, DPAD, P, true>), dim3((unsigned)nb), dim3(TK_NW * 64), 0, s, a);
   else hipLaunchKernelGGL((ivf_range_kernel<T, DPAD, P, false>), dim3((unsigned)nb), dim3(TK_NW * 64), 0, s, a);
   return hipGetLastError();
 }
 
 template <typename T, int DPAD>
-static hipError_t launch_ir(int P, bool fill, const IvfRangeArgs& a, hipStream_t s) {
+static hipError_t launch_ir(int P, bool fill, int64_t nb, const IvfRangeArgs& a, hipStream_t s) {
   constexpr int PF = range_blocks(DPAD / 4 / Elem<T>::V);
-  if (P == 1) return launch_ir_p<T, DPAD, 1>(fill, a, s);
-  if (P == PF) return launch_ir_p<T, DPAD, PF>(fill, a, s);
+  if (P == 1) return launch_ir_p<T, DPAD, 1>(fill, nb, a, s);
+  if (P == PF) return launch_ir_p<T, DPAD, PF>(fill, nb, a, s);
   return hipErrorInvalidValue;
 }
 
-// Pair blocks per wave: one block for a small batch of pairs, so more waves share the work (the
-// scan's rule)
+// Pair blocks per wave: range_blocks, then walk_blocks over the pairs (the scan's rule)
 int ivf_range_blocks(int dtype, int dpad, int64_t npairs) {
-  const int P = range_blocks(dpad / 4 / (dtype == DT_BF16 ? 8 : 4));
-  return (P > 1 && npairs < (int64_t)32768 * P) ? 1 : P;
+  return walk_blocks(range_blocks(dpad / 4 / (dtype == DT_BF16 ? 8 : 4)), npairs);
 }
 
 hipError_t launch_ivf_range(int dtype, int dpad, int P, bool fill, const IvfRangeArgs& a, hipStream_t s) {
-  if (a.npairs <= 0 || a.max_items <= 0) return hipSuccess;
+  int64_t nb;
+  if (const hipError_t e = ivf_walk_grid(a.w, dpad, nb); e != hipSuccess || nb == 0) return e;
   if (fill && a.total <= 0) return hipSuccess;
-  if (a.K < 1 || a.nprobe < 1 || a.D > dpad || a.total < 0) return hipErrorInvalidValue;
-  if ((a.max_items + TK_NW - 1) / TK_NW > 0x7fffffff) return hipErrorInvalidValue;
+  if (a.total < 0) return hipErrorInvalidValue;
   return (hipError_t)for_width(dtype, dpad, [&](auto t, auto w) {
-    return launch_ir<typename decltype(t)::type, decltype(w)::value>(P, fill, a, s);
+    return launch_ir<typename decltype(t)::type, decltype(w)::value>(P, fill, nb, a, s);
   });
 }
 

@@ -80,10 +80,8 @@ static hipError_t launch_tk_p(const TopkArgs& a, hipStream_t s) {
 template <typename T, int DPAD, int M>
 static hipError_t launch_tk_m(const TopkArgs& a, hipStream_t s) {
   constexpr int P = topk_blocks(DPAD / 4 / Elem<T>::V, M);
-  // a small batch takes one block per wave, so more waves share the work (under ~2 waves
-  // per SIMD of a 256-CU part otherwise)
-  if (P > 1 && a.N < (int64_t)32768 * P) return launch_tk_p<T, DPAD, 1, M>(a, s);
-  return launch_tk_p<T, DPAD, P, M>(a, s);
+  // (a small batch takes one block per wave: walk.h)
+  return walk_blocks(P, a.N) == 1 ? launch_tk_p<T, DPAD, 1, M>(a, s) : launch_tk_p<T, DPAD, P, M>(a, s);
 }
 
 template <typename T, int DPAD>

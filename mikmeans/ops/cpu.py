@@ -333,28 +333,37 @@ def index_repack(rows_old: torch.Tensor, cn_old: torch.Tensor, offsets_old: torc
     cn[dst] = cn_old[src]
 
 
-def index_search(index, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: int) -> torch.Tensor:
-    """Sorted search keys int64 [nq, m] (``d2 bits << 32 | row``, ``IVF_EMPTY_KEY`` padded) over
-    the lists of every query's ``nprobe`` nearest centres (:func:`topk`'s indices).  ``d2`` is
-    :func:`topk`'s form with the indexed rows in the place of the centres."""
-    K, dev = index.K, Q.device
-    nq = Q.shape[0]
+def _index_rows(index, D: int):
+    """The indexed rows in list order: ``(lid, rid, c, cn)`` -- every position's list and row id, the
+    rows themselves (float32, ``D`` columns) and their squared norms, gathered from the pack's tiles."""
+    K, dev = index.K, index.order.device
     sizes = index.offsets[1:] - index.offsets[:-1]
     nv = int(index.offsets[K])
     lid = torch.repeat_interleave(torch.arange(K, dtype=torch.int64, device=dev), sizes)       # list of position p
     slot = index.tile_offsets[lid] * 16 + torch.arange(nv, dtype=torch.int64, device=dev) - index.offsets[lid]
-    rid = index.order[:nv]
     store = index.pack.view(-1, index.cols)
-    c = store[slot][:, : Q.shape[1]].to(torch.float32)
-    cn = index.cn[slot]
+    return lid, index.order[:nv], store[slot][:, :D].to(torch.float32), index.cn[slot]
+
+
+def _block_d2(Qb: torch.Tensor, c: torch.Tensor, cn: torch.Tensor) -> torch.Tensor:
+    """Clamped squared distances [queries, rows] of a block of queries, in :func:`topk`'s form."""
+    xb = Qb.to(torch.float32)
+    return ((xb * xb).sum(1)[:, None] + (cn[None, :] - 2.0 * (xb @ c.T))).clamp_min(0.0) + 0.0   # (-0 -> +0)
+
+
+def index_search(index, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: int) -> torch.Tensor:
+    """Sorted search keys int64 [nq, m] (``d2 bits << 32 | row``, ``IVF_EMPTY_KEY`` padded) over
+    the lists of every query's ``nprobe`` nearest centres (:func:`topk`'s indices).  ``d2`` is
+    :func:`topk`'s form with the indexed rows in the place of the centres."""
+    K, dev, nq = index.K, Q.device, Q.shape[0]
+    lid, rid, c, cn = _index_rows(index, Q.shape[1])
     probes = topk(Q, centers, nprobe)[0].to(torch.int64)
     keys = torch.full((nq, m), IVF_EMPTY_KEY, dtype=torch.int64, device=dev)
-    rows = max(1, (1 << 24) // max(nv, 1))
+    rows = max(1, (1 << 24) // max(rid.numel(), 1))
     for s in range(0, nq, rows):
-        xb = Q[s : s + rows].to(torch.float32)
-        d = ((xb * xb).sum(1)[:, None] + (cn[None, :] - 2.0 * (xb @ c.T))).clamp_min(0.0) + 0.0   # (-0 -> +0)
+        d = _block_d2(Q[s : s + rows], c, cn)
         key = (d.contiguous().view(torch.int32).to(torch.int64) << 32) | rid[None, :]
-        member = torch.zeros((xb.shape[0], K), dtype=torch.bool, device=dev)
+        member = torch.zeros((d.shape[0], K), dtype=torch.bool, device=dev)
         member.scatter_(1, probes[s : s + rows], True)
         key = torch.where(member[:, lid], key, IVF_EMPTY_KEY).sort(dim=1).values[:, :m]
         keys[s : s + rows, : key.shape[1]] = key
@@ -369,25 +378,16 @@ def index_range(index, Q: torch.Tensor, centers: torch.Tensor, r2: torch.Tensor,
     after probe and in list order within a probe.  ``count_only``: ``counts int64 [nq]`` alone;
     ``want_probe``: also every hit's probe rank.  ``r2``: float32 [nq], finite and non-negative (a
     NaN or infinite ``d2`` is no hit)."""
-    K, dev = index.K, Q.device
-    nq = Q.shape[0]
-    sizes = index.offsets[1:] - index.offsets[:-1]
-    nv = int(index.offsets[K])
-    lid = torch.repeat_interleave(torch.arange(K, dtype=torch.int64, device=dev), sizes)       # list of position p
-    slot = index.tile_offsets[lid] * 16 + torch.arange(nv, dtype=torch.int64, device=dev) - index.offsets[lid]
-    rid = index.order[:nv]
-    store = index.pack.view(-1, index.cols)
-    c = store[slot][:, : Q.shape[1]].to(torch.float32)
-    cn = index.cn[slot]
+    K, dev, nq = index.K, Q.device, Q.shape[0]
+    lid, rid, c, cn = _index_rows(index, Q.shape[1])
     probes = topk(Q, centers, nprobe)[0].to(torch.int64) if nq else torch.zeros((0, nprobe), dtype=torch.int64, device=dev)
     counts = torch.zeros(nq, dtype=torch.int64, device=dev)
     keys, ranks = [], []
-    rows = max(1, (1 << 24) // max(nv, 1))
+    rows = max(1, (1 << 24) // max(rid.numel(), 1))
     for s in range(0, nq, rows):
-        xb = Q[s : s + rows].to(torch.float32)
-        d = ((xb * xb).sum(1)[:, None] + (cn[None, :] - 2.0 * (xb @ c.T))).clamp_min(0.0) + 0.0   # (-0 -> +0)
-        prank = torch.full((xb.shape[0], K), nprobe, dtype=torch.int64, device=dev)            # a list's probe rank
-        prank.scatter_(1, probes[s : s + rows], torch.arange(nprobe, dtype=torch.int64, device=dev).expand(xb.shape[0], -1))
+        d = _block_d2(Q[s : s + rows], c, cn)
+        prank = torch.full((d.shape[0], K), nprobe, dtype=torch.int64, device=dev)            # a list's probe rank
+        prank.scatter_(1, probes[s : s + rows], torch.arange(nprobe, dtype=torch.int64, device=dev).expand(d.shape[0], -1))
         pr = prank[:, lid]
         hit = (pr < nprobe) & (d <= r2[s : s + rows, None])
         counts[s : s + rows] = hit.sum(1)

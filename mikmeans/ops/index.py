@@ -23,7 +23,8 @@ from . import TOPK_NATIVE_MAX, cpu, pad_columns, row_sqnorm, topk, topk_blocks
 from .native import dpad_for, dtype_code, require
 
 __all__ = ["PARTITION_MAX_K", "IVF_EMPTY_KEY", "INDEX_MAX_M", "INDEX_SCAN_KEYS", "partition", "RowIndex",
-           "index_tiles", "index_build", "index_add", "index_remove", "index_search", "index_range", "index_decode"]
+           "index_tiles", "pair_items", "index_build", "index_add", "index_remove", "index_search", "index_range",
+           "index_decode"]
 
 PARTITION_MAX_K = cpu.PARTITION_MAX_K   # csrc/kernels.h (the extension exports the same number)
 IVF_EMPTY_KEY = cpu.IVF_EMPTY_KEY       # a result slot without a row: behind every key
@@ -92,6 +93,47 @@ def _native_cols(Xp: torch.Tensor) -> int:
     return dpad_for(Xp.shape[1], Xp.dtype) if Xp.is_cuda else 0
 
 
+def _nearest_lists(labels: torch.Tensor, start: int, blocks, centers, block_rows, like: RowIndex | None = None):
+    """``labels[start + i]`` = the list of row i of ``blocks``: :func:`topk`'s first column, -1 where its
+    distance is NaN or infinite.  Returns the rows' ``(D, dtype, native cols)``, which must be those of
+    the index ``like`` where one is given."""
+    shape = None
+    for s, Xt, pk in blocks():
+        Xp = pad_columns(Xt) if Xt.is_cuda else Xt
+        held = like is not None and (like.D, like.dtype, labels.device)
+        if held and (Xp.dim() != 2 or (Xp.shape[1], Xp.dtype, Xp.device) != held):
+            raise ValueError(f"the index holds rows of {like.D} {like.dtype} features on {labels.device}, got "
+                             f"{tuple(Xp.shape)} {Xp.dtype} on {Xp.device}")
+        shape = (Xp.shape[1], Xp.dtype, _native_cols(Xp))
+        for s2, idx, d2 in topk_blocks(Xp, centers, 1, pack=pk, block_rows=block_rows):
+            a = start + s + s2
+            labels[a : a + idx.shape[0]] = torch.where(torch.isfinite(d2[:, 0]), idx[:, 0], -1)
+    return shape
+
+
+def _layout(labels: torch.Tensor, K: int, cols: int, dtype):
+    """``(order, offsets, rpos, toff, rpack, cn)`` of the index whose ids have the lists ``labels``:
+    the partition, every list's first tile and an empty row pack (zeros, ``PAD_SCORE`` in ``cn``)."""
+    n, dev = labels.numel(), labels.device
+    order, offsets, rpos = partition(labels, K, want_pos=True)
+    sizes = offsets[1:] - offsets[:-1]
+    toff = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    toff[1:] = torch.cumsum((sizes + 15) // 16, 0)
+    tiles = index_tiles(n, K)
+    rpack = torch.zeros(tiles * 16 * cols, dtype=dtype, device=dev)
+    cn = torch.full((tiles * 16,), cpu.PAD_SCORE, dtype=torch.float32, device=dev)
+    return order, offsets, rpos, toff, rpack, cn
+
+
+def _pack_rows(blocks, start: int, native: bool, cols: int, labels, rpos, offsets, toff, rpack, cn) -> None:
+    """The rows of ``blocks`` (ids from ``start`` on) into the row pack."""
+    for s, Xt, _ in blocks():
+        if native:
+            require().ivf_pack(pad_columns(Xt), start + s, labels, rpos, offsets, toff, rpack, cn, cols)
+        else:
+            cpu.index_pack(Xt, start + s, labels, rpos, offsets, toff, rpack.view(-1, cols), cn)
+
+
 def index_build(X, centers: torch.Tensor, *, pack=None, block_rows: int | None = None, blocks=None,
                 n: int | None = None) -> RowIndex:
     """Index the rows of ``X`` under ``centers``.  A row's list is :func:`topk`'s first column (the
@@ -105,28 +147,11 @@ def index_build(X, centers: torch.Tensor, *, pack=None, block_rows: int | None =
     n, K = int(n), int(centers.shape[0])
     if n >= 1 << 32:
         raise ValueError(f"an index takes fewer than 2^32 rows, got {n}")
-    dev = centers.device
-    labels = torch.empty(n, dtype=torch.int32, device=dev)
-    shape = None
-    for s, Xt, pk in blocks():
-        Xp = pad_columns(Xt) if Xt.is_cuda else Xt
-        shape = (Xp.shape[1], Xp.dtype, _native_cols(Xp))
-        for s2, idx, d2 in topk_blocks(Xp, centers, 1, pack=pk, block_rows=block_rows):
-            labels[s + s2 : s + s2 + idx.shape[0]] = torch.where(torch.isfinite(d2[:, 0]), idx[:, 0], -1)
-    D, dtype, dpad = shape
-    order, offsets, rpos = partition(labels, K, want_pos=True)
-    sizes = offsets[1:] - offsets[:-1]
-    toff = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-    toff[1:] = torch.cumsum((sizes + 15) // 16, 0)
+    labels = torch.empty(n, dtype=torch.int32, device=centers.device)
+    D, dtype, dpad = _nearest_lists(labels, 0, blocks, centers, block_rows)
     cols = dpad or D
-    tiles = index_tiles(n, K)
-    rpack = torch.zeros(tiles * 16 * cols, dtype=dtype, device=dev)
-    cn = torch.full((tiles * 16,), cpu.PAD_SCORE, dtype=torch.float32, device=dev)
-    for s, Xt, _ in blocks():
-        if dpad:
-            require().ivf_pack(pad_columns(Xt), s, labels, rpos, offsets, toff, rpack, cn, dpad)
-        else:
-            cpu.index_pack(Xt, s, labels, rpos, offsets, toff, rpack.view(tiles * 16, cols), cn)
+    order, offsets, rpos, toff, rpack, cn = _layout(labels, K, cols, dtype)
+    _pack_rows(blocks, 0, bool(dpad), cols, labels, rpos, offsets, toff, rpack, cn)
     return RowIndex(n, K, D, dtype, bool(dpad), cols, rpack, cn, order, offsets, toff)
 
 
@@ -150,25 +175,16 @@ def _update(index: RowIndex, labels: torch.Tensor, rpos_old: torch.Tensor, block
     partition, fresh buffers, the rows of ``index`` that keep a list copied from its pack (they
     keep their list: only -1 may replace a label) and the rows of ``blocks`` -- ``(start, rows,
     centre pack)`` with ``start`` counted from ``index.n`` -- packed behind them."""
-    n, K, dev = labels.numel(), index.K, labels.device
-    order, offsets, rpos = partition(labels, K, want_pos=True)
-    sizes = offsets[1:] - offsets[:-1]
-    toff = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-    toff[1:] = torch.cumsum((sizes + 15) // 16, 0)
-    cols, tiles = index.cols, index_tiles(n, K)
-    rpack = torch.zeros(tiles * 16 * cols, dtype=index.dtype, device=dev)
-    cn = torch.full((tiles * 16,), cpu.PAD_SCORE, dtype=torch.float32, device=dev)
+    n, K, cols = labels.numel(), index.K, index.cols
+    order, offsets, rpos, toff, rpack, cn = _layout(labels, K, cols, index.dtype)
     if index.native:
         require().ivf_repack(index.pack, index.cn, index.offsets, index.tile_offsets, rpos_old, order, offsets, toff,
                              rpack, cn, index.D, cols)
     else:
         cpu.index_repack(index.pack.view(-1, cols), index.cn, index.offsets, index.tile_offsets, rpos_old, labels, rpos,
-                         offsets, toff, rpack.view(tiles * 16, cols), cn)
-    for s, Xt, _ in (blocks() if blocks is not None else ()):
-        if index.native:
-            require().ivf_pack(pad_columns(Xt), index.n + s, labels, rpos, offsets, toff, rpack, cn, cols)
-        else:
-            cpu.index_pack(Xt, index.n + s, labels, rpos, offsets, toff, rpack.view(tiles * 16, cols), cn)
+                         offsets, toff, rpack.view(-1, cols), cn)
+    if blocks is not None:
+        _pack_rows(blocks, index.n, index.native, cols, labels, rpos, offsets, toff, rpack, cn)
     return RowIndex(n, K, index.D, index.dtype, index.native, cols, rpack, cn, order, offsets, toff)
 
 
@@ -192,14 +208,7 @@ def index_add(index: RowIndex, X, centers: torch.Tensor, *, pack=None, block_row
     dev = index.order.device
     labels = torch.empty(n0 + n1, dtype=torch.int32, device=dev)
     labels[:n0], rpos_old = _id_lists(index)
-    for s, Xt, pk in blocks():
-        Xp = pad_columns(Xt) if Xt.is_cuda else Xt
-        if Xp.dim() != 2 or (Xp.shape[1], Xp.dtype, Xp.device) != (index.D, index.dtype, dev):
-            raise ValueError(f"the index holds rows of {index.D} {index.dtype} features on {dev}, got "
-                             f"{tuple(Xp.shape)} {Xp.dtype} on {Xp.device}")
-        for s2, idx, d2 in topk_blocks(Xp, centers, 1, pack=pk, block_rows=block_rows):
-            a = n0 + s + s2
-            labels[a : a + idx.shape[0]] = torch.where(torch.isfinite(d2[:, 0]), idx[:, 0], -1)
+    _nearest_lists(labels, n0, blocks, centers, block_rows, like=index)
     return _update(index, labels, rpos_old, blocks)
 
 
@@ -223,20 +232,46 @@ def index_remove(index: RowIndex, ids: torch.Tensor):
     return _update(index, torch.where(gone, -1, labels), rpos_old), removed
 
 
+def pair_items(index: RowIndex, probes: torch.Tensor, P: int):
+    """The work items of a walk over the lists ``probes`` (int [nq, nprobe]) names, ``P`` blocks of 16
+    pairs an item (csrc/walk.h): ``(porder, poff, icum, max_items)`` -- the pair ids
+    ``q * nprobe + j`` grouped by list, where each list's pairs start, the cumulative item counts
+    and the grid bound ``walk_max_items``, which needs no host read.  The only place ``icum`` is
+    formed."""
+    npairs, per = probes.numel(), 16 * int(P)
+    porder, poff = partition(probes.reshape(-1), index.K)
+    icum = torch.zeros(index.K + 1, dtype=torch.int64, device=probes.device)
+    icum[1:] = torch.cumsum((poff[1:] - poff[:-1] + per - 1) // per, 0)
+    return porder, poff, icum, npairs // per + min(index.K, npairs)
+
+
+def _walk_args(index: RowIndex, Qp: torch.Tensor, probes: torch.Tensor, P: int, *mid) -> tuple:
+    """The leading arguments of ``ivf_scan`` / ``ivf_range`` (``mid``: what the op takes after ``qn``)."""
+    porder, poff, icum, max_items = pair_items(index, probes, P)
+    return (Qp, row_sqnorm(Qp), *mid, index.pack, index.cn, index.offsets, index.tile_offsets, index.order, porder,
+            poff, icum, probes.shape[1], index.cols, P, max_items)
+
+
 def _scan(index: RowIndex, Qp: torch.Tensor, probes: torch.Tensor, m: int) -> torch.Tensor:
     """Sorted keys int64 [nq, m] of one block of queries (native)."""
     C = require()
     nq, nprobe = probes.shape
-    npairs = nq * nprobe
-    porder, poff = partition(probes.reshape(-1), index.K)      # pair id = q * nprobe + j, grouped by list
-    P = C.ivf_scan_blocks(dtype_code(Qp.dtype), index.cols, m, npairs)
-    per = 16 * P
-    icum = torch.zeros(index.K + 1, dtype=torch.int64, device=Qp.device)
-    icum[1:] = torch.cumsum((poff[1:] - poff[:-1] + per - 1) // per, 0)
-    out = torch.empty((npairs, m), dtype=torch.int64, device=Qp.device)
-    C.ivf_scan(Qp, row_sqnorm(Qp), index.pack, index.cn, index.offsets, index.tile_offsets, index.order, porder, poff,
-               icum, nprobe, index.cols, P, npairs // per + min(index.K, npairs), out)
+    P = C.ivf_scan_blocks(dtype_code(Qp.dtype), index.cols, m, nq * nprobe)
+    out = torch.empty((nq * nprobe, m), dtype=torch.int64, device=Qp.device)
+    C.ivf_scan(*_walk_args(index, Qp, probes, P), out)
     return out.view(nq, nprobe * m).sort(dim=1).values[:, :m]   # unique keys: any sort gives one order
+
+
+def _check_queries(what: str, index: RowIndex, Q: torch.Tensor, nprobe: int) -> torch.Tensor:
+    """The queries of a ``what`` ("search" / "range search") as the index takes them (columns padded
+    on the GPU), or a ValueError."""
+    if not 1 <= nprobe <= index.K:
+        raise ValueError(f"{what} needs 1 <= nprobe <= n_clusters ({index.K}), got nprobe = {nprobe}")
+    Qp = pad_columns(Q) if Q.is_cuda else Q
+    if Qp.shape[1] != index.D or Qp.dtype != index.dtype or Qp.device != index.pack.device:
+        raise ValueError(f"{what} needs queries of {index.D} {index.dtype} features on {index.pack.device}, got "
+                         f"{Qp.shape[1]} {Qp.dtype} on {Qp.device}")
+    return Qp
 
 
 def index_search(index: RowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: int, *,
@@ -249,12 +284,7 @@ def index_search(index: RowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int
     m, nprobe = int(m), int(nprobe)
     if not 1 <= m <= INDEX_MAX_M:
         raise ValueError(f"search needs 1 <= m <= {INDEX_MAX_M}, got m = {m}")
-    if not 1 <= nprobe <= index.K:
-        raise ValueError(f"search needs 1 <= nprobe <= n_clusters ({index.K}), got nprobe = {nprobe}")
-    Qp = pad_columns(Q) if Q.is_cuda else Q
-    if Qp.shape[1] != index.D or Qp.dtype != index.dtype or Qp.device != index.pack.device:
-        raise ValueError(f"search needs queries of {index.D} {index.dtype} features on {index.pack.device}, got "
-                         f"{Qp.shape[1]} {Qp.dtype} on {Qp.device}")
+    Qp = _check_queries("search", index, Q, nprobe)
     nq = Qp.shape[0]
     if not index.native:
         return cpu.index_search(index, Qp, centers, m, nprobe)
@@ -273,17 +303,10 @@ def _range_block(index: RowIndex, Qp: torch.Tensor, probes: torch.Tensor, r2: to
     after query, probe after probe) and in list order within a pair.  The fill pass costs one host
     read of the block's total."""
     C = require()
-    nq, nprobe = probes.shape
-    npairs = nq * nprobe
-    dev = Qp.device
-    porder, poff = partition(probes.reshape(-1), index.K)      # pair id = q * nprobe + j, grouped by list
+    npairs, dev = probes.numel(), Qp.device
     P = C.ivf_range_blocks(dtype_code(Qp.dtype), index.cols, npairs)
-    per = 16 * P
-    icum = torch.zeros(index.K + 1, dtype=torch.int64, device=dev)
-    icum[1:] = torch.cumsum((poff[1:] - poff[:-1] + per - 1) // per, 0)
     counts = torch.zeros(npairs, dtype=torch.int64, device=dev)
-    args = (Qp, row_sqnorm(Qp), r2, index.pack, index.cn, index.offsets, index.tile_offsets, index.order, porder, poff,
-            icum, nprobe, index.cols, P, npairs // per + min(index.K, npairs), counts)
+    args = (*_walk_args(index, Qp, probes, P, r2), counts)
     C.ivf_range(*args)
     if count_only:
         return counts, None
@@ -316,12 +339,7 @@ def index_range(index: RowIndex, Q: torch.Tensor, centers: torch.Tensor, r2, npr
     nprobe = int(nprobe)
     if Q.dim() != 2:
         raise ValueError(f"range search needs queries [nq, D], got shape {tuple(Q.shape)}")
-    if not 1 <= nprobe <= index.K:
-        raise ValueError(f"range search needs 1 <= nprobe <= n_clusters ({index.K}), got nprobe = {nprobe}")
-    Qp = pad_columns(Q) if Q.is_cuda else Q
-    if Qp.shape[1] != index.D or Qp.dtype != index.dtype or Qp.device != index.pack.device:
-        raise ValueError(f"range search needs queries of {index.D} {index.dtype} features on {index.pack.device}, "
-                         f"got {Qp.shape[1]} {Qp.dtype} on {Qp.device}")
+    Qp = _check_queries("range search", index, Q, nprobe)
     nq, dev = Qp.shape[0], Qp.device
     r2 = torch.as_tensor(r2, dtype=torch.float32, device=dev)
     if r2.dim() > 1 or (r2.dim() == 1 and r2.shape[0] != nq):

@@ -136,6 +136,7 @@ class KernelResources:
     vgprs: int
     vgpr_spills: int
     scratch_bytes: int   # .private_segment_fixed_size
+    lds_bytes: int = 0   # .group_segment_fixed_size (static LDS of a workgroup)
 
 
 def kernel_resources(elf: Path) -> list[KernelResources]:
@@ -148,14 +149,29 @@ def kernel_resources(elf: Path) -> list[KernelResources]:
         vg = re.search(r"\.vgpr_count:\s+(\d+)", blk)
         sp = re.search(r"\.vgpr_spill_count:\s+(\d+)", blk)
         pr = re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk)
+        gs = re.search(r"\.group_segment_fixed_size:\s+(\d+)", blk)
         if name and vg:
             raw.append((name.group(1), int(vg.group(1)), int(sp.group(1)) if sp else 0,
-                        int(pr.group(1)) if pr else 0))
+                        int(pr.group(1)) if pr else 0, int(gs.group(1)) if gs else 0))
     dem = subprocess.run(["c++filt"], input="\n".join(x[0] for x in raw), capture_output=True,
                          text=True).stdout.splitlines() if raw else []
     if len(dem) != len(raw):
         dem = [x[0] for x in raw]
-    return [KernelResources(d, v, s_, p_) for (_, v, s_, p_), d in zip(raw, dem)]
+    return [KernelResources(d, v, s_, p_, g_) for (_, v, s_, p_, g_), d in zip(raw, dem)]
+
+
+def kernels(src_name: str, kernel: str, tmp_path: Path) -> dict[tuple[str, ...], KernelResources]:
+    """{template arguments: resources} of one kernel's instantiations in a built gfx950 object."""
+    from mikmeans import _build
+
+    src = _build.CSRC / src_name
+    obj = _build._compile(src, _build.source_flags(src.name), verbose=False)      # (the production object, cached)
+    out = {}
+    for r in kernel_resources(device_elf(obj, tmp_path / f"{src.stem}.dev.o")):
+        if f"{kernel}<" in r.name:
+            inner = r.name[r.name.index(f"{kernel}<") + len(kernel) + 1:]
+            out[tuple(a.strip() for a in inner[: inner.rindex(">(")].split(","))] = r
+    return out
 
 
 def assign16_template_args(demangled: str) -> list[str] | None:

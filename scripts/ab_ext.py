@@ -153,25 +153,45 @@ def cmd_run(a) -> int:
                              torch.empty((a.n, a.m), dtype=torch.int32, device=dev)))
         t["m"].topk(eng.X, t["pack"], t["cn"], a.k, t["kpad"], dpad, eng.xn, *t["out"])
 
-    if a.what == "ivf_scan":   # one index, one set of probes and pairs (the head module's) for every module's scan
+    if a.what in ("ivf_scan", "ivf_range"):   # one index, one set of probes and pairs (the head's) for every module
         from mikmeans import ops
         from mikmeans.ops import index as ix
 
+        head = mods["head"]
         index, Q = ix.index_build(eng.X, Cen), eng.X[: a.nq]
-        porder, poff = ix.partition(ops.topk(Q, Cen, a.nprobe)[0].reshape(-1), a.k)
-        npairs = Q.shape[0] * a.nprobe
-        per16 = 16 * mods["head"].ivf_scan_blocks(code, dpad, a.m, npairs)
-        icum = torch.zeros(a.k + 1, dtype=torch.int64, device=dev)
-        icum[1:] = torch.cumsum((poff[1:] - poff[:-1] + per16 - 1) // per16, 0)
-        scan = (Q, ops.row_sqnorm(Q), index.pack, index.cn, index.offsets, index.tile_offsets, index.order, porder,
-                poff, icum, a.nprobe, dpad, per16 // 16, npairs // per16 + min(a.k, npairs))
+        probes, npairs = ops.topk(Q, Cen, a.nprobe)[0], Q.shape[0] * a.nprobe
+
+        def walk(P, *mid):   # the leading arguments of ivf_scan / ivf_range
+            porder, poff, icum, max_items = ix.pair_items(index, probes, P)
+            return (Q, ops.row_sqnorm(Q), *mid, index.pack, index.cn, index.offsets, index.tile_offsets, index.order,
+                    porder, poff, icum, a.nprobe, dpad, P, max_items)
+
+        scan = walk(head.ivf_scan_blocks(code, dpad, a.m, npairs))
+    if a.what == "ivf_range":   # the radius: the head scan's m-th key per query; base: the head's counts
+        keys = torch.empty((npairs, a.m), dtype=torch.int64, device=dev)
+        head.ivf_scan(*scan, keys)
+        kth = keys.view(Q.shape[0], a.nprobe * a.m).sort(dim=1).values[:, a.m - 1]
+        r2 = torch.nan_to_num(ix.index_decode(kth)[1], nan=0.0).contiguous()   # (fewer than m rows probed: 0)
+        rng = walk(head.ivf_range_blocks(code, dpad, npairs), r2)
+        counts = torch.zeros(npairs, dtype=torch.int64, device=dev)
+        head.ivf_range(*rng, counts)
+        end = torch.cumsum(counts, 0)
+        rbase, total = end - counts, int(end[-1])
 
     def run_ivf_scan(t):   # the --m nearest indexed rows of every (query, probed list) pair
-        t.setdefault("out", (torch.empty((scan[0].shape[0] * a.nprobe, a.m), dtype=torch.int64, device=dev),))
+        t.setdefault("out", (torch.empty((npairs, a.m), dtype=torch.int64, device=dev),))
         t["m"].ivf_scan(*scan, t["out"][0])
 
+    def run_ivf_range(t):  # the count pass, then the fill pass: every row within the radius, per pair
+        t.setdefault("out", (torch.zeros(npairs, dtype=torch.int64, device=dev),
+                             torch.zeros(total, dtype=torch.int64, device=dev)))
+        t["m"].ivf_range(*rng, t["out"][0])
+        if total:
+            t["m"].ivf_range(*rng, t["out"][0], rbase, t["out"][1])
+
     fn = {"update": run_update, "blobs": run_blobs, "colstats": run_colstats, "rownorms": run_rownorms,
-          "transform": run_transform, "topk": run_topk, "ivf_scan": run_ivf_scan}.get(a.what, run_assign)
+          "transform": run_transform, "topk": run_topk, "ivf_scan": run_ivf_scan,
+          "ivf_range": run_ivf_range}.get(a.what, run_assign)
     for t in per.values():          # warm-up (kernel attributes, code objects)
         fn(t)
     torch.cuda.synchronize()
@@ -192,7 +212,7 @@ def cmd_run(a) -> int:
     if a.what == "rownorms":        # the same bits from every module
         for tag, t in per.items():
             t["same"] = bool(torch.equal(t["rn"], per["head"]["rn"]))
-    if a.what in ("transform", "topk", "ivf_scan"):   # the same bits from every module
+    if a.what in ("transform", "topk", "ivf_scan", "ivf_range"):   # the same bits from every module
         for tag, t in per.items():
             t["same"] = all(torch.equal(x.view(torch.int32), y.view(torch.int32))
                             for x, y in zip(t["out"], per["head"]["out"]))
@@ -233,10 +253,11 @@ def main(argv=None) -> int:
     r.add_argument("--rounds", type=int, default=5)
     r.add_argument("--reps", type=int, default=5)
     r.add_argument("--what", default="assign", choices=["assign", "update", "blobs", "colstats", "rownorms",
-                                                        "transform", "topk", "ivf_scan"])
-    r.add_argument("--m", type=int, default=8, help="topk / ivf_scan: list length")
-    r.add_argument("--nq", type=int, default=10_000, help="ivf_scan: queries (the first rows)")
-    r.add_argument("--nprobe", type=int, default=16, help="ivf_scan: lists probed per query")
+                                                        "transform", "topk", "ivf_scan", "ivf_range"])
+    r.add_argument("--m", type=int, default=8,
+                   help="topk / ivf_scan: list length; ivf_range: the radius is the m-th nearest row's distance")
+    r.add_argument("--nq", type=int, default=10_000, help="ivf_scan / ivf_range: queries (the first rows)")
+    r.add_argument("--nprobe", type=int, default=16, help="ivf_scan / ivf_range: lists probed per query")
     a = ap.parse_args(argv)
     if a.cmd == "build":
         cmd_build(a.ref)

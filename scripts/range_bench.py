@@ -53,17 +53,11 @@ def phases(index, Q, C, pk, r2, nprobe, repeats):
     for r in range(repeats + 1):
         (probes, _), a = _timed(lambda: ops.topk(Q, C, nprobe, pack=pk))
 
-        def part():
-            porder, poff = ops.partition(probes.reshape(-1), index.K)
-            P = ext.ivf_range_blocks(dtype_code(Q.dtype), index.cols, npairs)
-            icum = torch.zeros(index.K + 1, dtype=torch.int64, device=Q.device)
-            icum[1:] = torch.cumsum((poff[1:] - poff[:-1] + 16 * P - 1) // (16 * P), 0)
-            return porder, poff, icum, P
-
-        (porder, poff, icum, P), b = _timed(part)
+        P = ext.ivf_range_blocks(dtype_code(Q.dtype), index.cols, npairs)
+        (porder, poff, icum, max_items), b = _timed(lambda: ops.pair_items(index, probes, P))
         counts = torch.zeros(npairs, dtype=torch.int64, device=Q.device)
         args = (Q, ops.row_sqnorm(Q), r2, index.pack, index.cn, index.offsets, index.tile_offsets, index.order, porder,
-                poff, icum, nprobe, index.cols, P, npairs // (16 * P) + min(index.K, npairs), counts)
+                poff, icum, nprobe, index.cols, P, max_items, counts)
         _, c = _timed(lambda: ext.ivf_range(*args))
 
         def scan():

@@ -327,3 +327,57 @@ def test_the_mirror_agrees_on_exact_data(native):
     assert not cpu_ix.native and gpu_ix.native
     assert torch.equal(cpu_ix.order, gpu_ix.order.cpu()) and torch.equal(cpu_ix.offsets, gpu_ix.offsets.cpu())
     assert torch.equal(ref.index_search(cpu_ix, Q, C, 8, 3), ops.index_search(gpu_ix, Q.to(DEV), C.to(DEV), 8, 3).cpu())
+
+
+# ------------------------------------------------------------------- the binding's checks
+def test_the_binding_refuses_a_wrong_walk(native):
+    """ivf_scan and ivf_range with the arguments ops.pair_items gives, one of them wrong at a time:
+    a P that is neither 1 nor the rule's, max_items one below and one above the accepted window
+    (from the full blocks alone, npairs // 16 P, to K + 1 above that), a pack that is not whole
+    tiles, a porder shorter than the pairs and an int32 icum are refused on the host (RuntimeError,
+    before any launch); the unmodified calls then give ops.index_search / ops.index_range."""
+    from mikmeans.ops.native import dtype_code, require
+
+    ext = require()
+    n, d, K, nq, nprobe, m = 70, 16, 3, 5, 2, 4
+    g = torch.Generator().manual_seed(70)
+    C = 8.0 * torch.randn(K, d, generator=g)
+    lab = torch.repeat_interleave(torch.arange(K), torch.tensor([0, 17, 53]))[torch.randperm(n, generator=g)]
+    X = (C[lab] + 0.25 * torch.randn(n, d, generator=g)).to(DEV)
+    Q = (X[torch.randint(0, n, (nq,), generator=g).to(DEV)].cpu() + 0.25 * torch.randn(nq, d, generator=g)).to(DEV)
+    C = C.to(DEV)
+    ix = ops.index_build(X, C)
+    assert ix.native and (ix.offsets[1:] - ix.offsets[:-1]).tolist() == [0, 17, 53]
+    probes, npairs, code = ops.topk(Q, C, nprobe)[0], nq * nprobe, dtype_code(torch.float32)
+    r2 = torch.full((nq,), 3.0, device=DEV)
+
+    def refusals(op, P, lead, tail):
+        porder, poff, icum, max_items = ops.pair_items(ix, probes, P)
+        good = [*lead, ix.pack, ix.cn, ix.offsets, ix.tile_offsets, ix.order, porder, poff, icum, nprobe, ix.cols, P,
+                max_items]
+        i_pack, i_porder, i_icum, i_P, i_max = (len(lead) + i for i in (0, 5, 7, 10, 11))
+        assert good[i_pack] is ix.pack and good[i_porder] is porder and good[i_icum] is icum and good[i_P] == P == 1
+        lo = npairs // (16 * P)
+        assert lo <= max_items <= lo + K + 1
+        for i, bad in ((i_P, 2), (i_max, lo - 1), (i_max, lo + K + 2), (i_pack, ix.pack[:-1]), (i_porder, porder[:-1]),
+                       (i_icum, icum.to(torch.int32))):
+            args = list(good)
+            args[i] = bad
+            with pytest.raises(RuntimeError):
+                op(*args, *tail)
+        op(*good, *tail)
+        return good
+
+    qn = ops.row_sqnorm(Q)
+    out = torch.empty((npairs, m), dtype=torch.int64, device=DEV)
+    refusals(ext.ivf_scan, ext.ivf_scan_blocks(code, ix.cols, m, npairs), [Q, qn], [out])
+    assert torch.equal(out.view(nq, nprobe * m).sort(dim=1).values[:, :m], ops.index_search(ix, Q, C, m, nprobe))
+
+    counts = torch.zeros(npairs, dtype=torch.int64, device=DEV)
+    good = refusals(ext.ivf_range, ext.ivf_range_blocks(code, ix.cols, npairs), [Q, qn, r2], [counts])
+    lims, ekeys = ops.index_range(ix, Q, C, r2, nprobe, sort=False)
+    end = torch.cumsum(counts, 0)
+    assert int(end[-1]) == ekeys.numel() > 0 and torch.equal(end.view(nq, nprobe)[:, -1], lims[1:])
+    keys = torch.empty(int(end[-1]), dtype=torch.int64, device=DEV)
+    ext.ivf_range(*good, counts, end - counts, keys)
+    assert torch.equal(keys, ekeys)

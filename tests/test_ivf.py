@@ -309,26 +309,12 @@ def test_plan_mirrors_the_native_partition_geometry():
         assert memplan.partition_blocks(n, K) == C.partition_blocks(n, K), (n, K)
 
 
-def _kernels(src_name, kernel, tmp_path):
-    """{template arguments: resources} of one kernel's instantiations in a built gfx950 object."""
-    from mikmeans import _build
-    from mikmeans.utils import isa
-
-    src = _build.CSRC / src_name
-    obj = _build._compile(src, _build.source_flags(src.name), verbose=False)      # (the production object, cached)
-    out = {}
-    for r in isa.kernel_resources(isa.device_elf(obj, tmp_path / f"{src.stem}.dev.o")):
-        if f"{kernel}<" in r.name:
-            inner = r.name[r.name.index(f"{kernel}<") + len(kernel) + 1:]
-            out[tuple(a.strip() for a in inner[: inner.rindex(">(")].split(","))] = r
-    return out
-
-
 def test_scan_kernels_register_budget(tmp_path):
     """Every scan instantiation keeps its lists in registers (no scratch, no spills) and fits two
     waves per SIMD (<= 256 VGPRs) wherever topk_kernel of the same (T, DPAD, P, M) does; the scan
     has exactly topk's instantiations."""
     from mikmeans import _build
+    from mikmeans.utils.isa import kernels as _kernels
 
     if shutil.which(_build._hipcc()) is None and not os.path.exists(_build._hipcc()):
         pytest.skip("hipcc not available")

@@ -65,3 +65,12 @@ def test_width_dispatch_under_asan_ubsan(tmp_path):
     """csrc/dispatch.h for_width, for both element sizes: a case for exactly the widths
     plan::assign_dpad returns over D = 1..1024, every other width in 1..2048 refused."""
     _run_harness(tmp_path, "width_fuzz")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_index_walk_items_under_asan_ubsan(tmp_path):
+    """csrc/walk.h, the work item of the scan, range and repack kernels: for 16, 48 and 64 pairs an
+    item and random per-list pair counts (empty lists, exactly PER, PER +- 1) the items cover every
+    pair once and in order, each with 1..PER pairs inside its list, their number stays within the
+    grid bound walk_max_items, and list_of is right at both ends and over runs of empty lists."""
+    _run_harness(tmp_path, "walk_fuzz")

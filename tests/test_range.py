@@ -306,25 +306,11 @@ def test_range_search_is_world_size_invariant():
             assert o["raised"] == one["raised"]
 
 
-def _kernels(src_name, kernel, tmp_path):
-    """{template arguments: resources} of one kernel's instantiations in a built gfx950 object."""
-    from mikmeans import _build
-    from mikmeans.utils import isa
-
-    src = _build.CSRC / src_name
-    obj = _build._compile(src, _build.source_flags(src.name), verbose=False)      # (the production object, cached)
-    out = {}
-    for r in isa.kernel_resources(isa.device_elf(obj, tmp_path / f"{src.stem}.dev.o")):
-        if f"{kernel}<" in r.name:
-            inner = r.name[r.name.index(f"{kernel}<") + len(kernel) + 1:]
-            out[tuple(a.strip() for a in inner[: inner.rindex(">(")].split(","))] = r
-    return out
-
-
 def test_range_kernels_register_budget(tmp_path):
     """Every instantiation of the count and the fill kernel runs without scratch or spills in at
     most 256 VGPRs (two waves per SIMD), and both cover every (dtype, padded width) of the scan."""
     from mikmeans import _build
+    from mikmeans.utils.isa import kernels as _kernels
 
     if shutil.which(_build._hipcc()) is None and not os.path.exists(_build._hipcc()):
         pytest.skip("hipcc not available")

@@ -83,26 +83,12 @@ def test_cpu_nonfinite_rows_and_centres_are_never_near(dtype):
         assert bool(torch.isfinite(d2[:, : K - 1]).all())
 
 
-def _kernels(src_name, kernel, tmp_path):
-    """{template arguments: resources} of one kernel's instantiations in a built gfx950 object."""
-    from mikmeans import _build
-    from mikmeans.utils import isa
-
-    src = _build.CSRC / src_name
-    obj = _build._compile(src, _build.source_flags(src.name), verbose=False)      # (the production object, cached)
-    out = {}
-    for r in isa.kernel_resources(isa.device_elf(obj, tmp_path / f"{src.stem}.dev.o")):
-        if f"{kernel}<" in r.name:
-            inner = r.name[r.name.index(f"{kernel}<") + len(kernel) + 1:]
-            out[tuple(a.strip() for a in inner[: inner.rindex(">(")].split(","))] = r
-    return out
-
-
 def test_topk_kernels_register_budget(tmp_path):
     """Every top-m instantiation keeps its lists in registers (no scratch, no spills: a list
     that moved to scratch passes every functional test, only slower), and wherever the transform
     kernel of the same (dtype, DPAD) fits two waves per SIMD (<= 256 VGPRs) so does the top-m."""
     from mikmeans import _build
+    from mikmeans.utils.isa import kernels as _kernels
 
     if shutil.which(_build._hipcc()) is None and not os.path.exists(_build._hipcc()):
         pytest.skip("hipcc not available")
