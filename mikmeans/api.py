@@ -468,6 +468,48 @@ class ClusterIndex:
         d = d2 if squared else d2.sqrt()
         return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
 
+    def search_deep(self, Q, m: int, *, nprobe: int = 8, squared: bool = False, passes: int | None = None):
+        """:meth:`search` for up to ``ops.INDEX_DEEP_MAX_M`` = 2048 rows a query: ``(rows [nq, m] int64,
+        distances [nq, m] float32)``, what :meth:`search` would return if its list were that long --
+        the first ``m`` of the ascending ``(d2 bits << 32 | row)`` keys over the rows of the query's
+        ``nprobe`` probed lists, equal distances by the lower row id, missing slots row -1 and
+        distance NaN -- and for ``m <= 32`` :meth:`search`'s result bit for bit.  ``nprobe``,
+        ``squared``, cosine models, numpy queries, host blocks and multi-rank jobs as in
+        :meth:`search`.
+
+        On the GPU no candidate list is kept: a radix select over the bits of the squared distances
+        (csrc/deep.hip: per 8-bit digit one histogram pass over the walk of :meth:`search` and one
+        select) finds a radius that is at least every query's m-th distance, and the two passes of
+        :meth:`range_search` collect the rows under it, which are sorted and cut to ``m``.  The
+        select stops as soon as the radius lets through at most ``ops.INDEX_DEEP_OVERSHOOT`` times
+        the rows wanted (one scalar host read a pass, one more for the fill); ``passes`` = 1..4
+        forces the pass count and does not change the result.  Rows tied with the m-th one are all
+        under the exact radius, so ties there make the rows collected exceed ``m`` by the number
+        of tied rows: inherent to the method, and the lower row ids are kept.  The memory plan
+        (``memplan.plan_index_search_deep``) is checked against the HBM budget up front.  Queries
+        with non-finite coordinates give unspecified results; the other queries' are unchanged."""
+        mdl, ix = self._model, self._index
+        m = int(m)
+        if not 1 <= m <= ops.INDEX_DEEP_MAX_M:
+            raise ValueError(f"search_deep needs 1 <= m <= {ops.INDEX_DEEP_MAX_M}, got m = {m}")
+        if passes is not None and not 1 <= int(passes) <= 4:
+            raise ValueError(f"search_deep needs passes in 1..4 (or None), got {passes}")
+        c, nprobe = self._probe_args("search_deep", Q, nprobe)
+        if ix.pack.is_cuda:
+            from .parallel import memplan
+
+            plan = memplan.plan_index_search_deep(ix.n, int(c.shape[1]), ix.K, ix.dtype, nq=int(Q.shape[0]), m=m,
+                                                  nprobe=nprobe)
+            plan.budget = memplan.hbm_budget(ix.pack.device) + sum(
+                plan.persistent[k] for k in ("row_pack", "cn", "order", "offsets", "tile_offsets"))   # (held already)
+            if not plan.fits:
+                raise memplan.HBMCapacityError(f"search_deep: {plan.summary()} does not fit")
+        (keys,), was_numpy = mdl._row_blocks(
+            Q, lambda Qt, pk: (ops.index_search_deep(ix, Qt, c, m, nprobe, pack=pk, passes=passes),))
+        rows, d2 = _merge_search_keys(keys, self._comm, self.row_start)
+        d = d2 if squared else d2.sqrt()
+        return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
+
     def _probe_args(self, what, Q, nprobe):
         """``(centres, nprobe)`` of a ``what`` ("search" / "range_search") over 2-D queries, checked."""
         c = self._model.cluster_centers_

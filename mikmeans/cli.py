@@ -9,7 +9,8 @@ Commands (the reference's top-bar controls, app.mjs:240-288, as a CLI):
                   simplified silhouette, Davies-Bouldin), as JSON; ``--exemplars M`` adds every
                   cluster's M nearest (``--farthest``: farthest) rows
 * ``search``   -- the M rows of a dataset nearest each query, through a saved model's clusters
-                  (``--nprobe P`` clusters searched per query; rows and distances as .npz), or with
+                  (``--nprobe P`` clusters searched per query; rows and distances as .npz; M up to
+                  32, with ``--deep`` up to 2048), or with
                   ``--radius R`` in place of ``--top M`` every row within R of each query (lims, rows
                   and distances as .npz)
 * ``blobs``    -- write a synthetic Gaussian-blob dataset
@@ -183,8 +184,8 @@ def cmd_report(a) -> int:
 
 def cmd_search(a) -> int:
     """Nearest-row search through a saved model's clusters (``KMeans.build_index`` /
-    ``ClusterIndex.search``): every rank indexes its shard of ``--input`` (or, in a one-rank job, loads
-    the saved index of ``--index``), all ranks search the same ``--queries``, the per-rank lists are
+    ``ClusterIndex.search``, with ``--deep`` ``ClusterIndex.search_deep``): every rank indexes its
+    shard of ``--input`` (or, in a one-rank job, loads the saved index of ``--index``), all ranks search the same ``--queries``, the per-rank lists are
     merged and rank 0 writes ``rows`` ([nq, M] int64, global row indices, -1 padded) and ``distances``
     ([nq, M] float32, NaN padded) to ``--output`` (.npz)."""
     from . import KMeans, ops
@@ -197,14 +198,17 @@ def cmd_search(a) -> int:
     if (a.top is None) == (a.radius is None):
         raise SystemExit("search: give one of --top M and --radius R")
     if a.radius is not None:
+        if a.deep:
+            raise SystemExit("search: --deep goes with --top M")
         return _search_radius(a, km, comm)
-    if not 1 <= a.top <= ops.INDEX_MAX_M:
-        raise SystemExit(f"search: --top must be in [1, {ops.INDEX_MAX_M}], got {a.top}")
+    most = ops.INDEX_DEEP_MAX_M if a.deep else ops.INDEX_MAX_M
+    if not 1 <= a.top <= most:
+        raise SystemExit(f"search: --top must be in [1, {most}], got {a.top}")
     if not 1 <= a.nprobe <= K:
         raise SystemExit(f"search: --nprobe must be in [1, {K}], got {a.nprobe}")
     index, n = _search_index(a, km, comm)
     Q = np.load(a.queries, allow_pickle=False)
-    rows, dist = index.search(Q, a.top, nprobe=a.nprobe, squared=a.squared)
+    rows, dist = (index.search_deep if a.deep else index.search)(Q, a.top, nprobe=a.nprobe, squared=a.squared)
     if comm.rank == 0:
         if a.output:
             np.savez(a.output, rows=rows.astype(np.int64), distances=dist.astype(np.float32))
@@ -555,7 +559,9 @@ def build_parser():
     sp.add_argument("--input", help="the rows to index (.npy / .safetensors / .csv)")
     sp.add_argument("--index", metavar="DIR", help="in place of --input: a saved index (mikmeans index) to load")
     sp.add_argument("--queries", required=True, help="the query rows (.npy)")
-    sp.add_argument("--top", type=int, metavar="M", help="rows per query (1..32)")
+    sp.add_argument("--top", type=int, metavar="M", help="rows per query (1..32; 1..2048 with --deep)")
+    sp.add_argument("--deep", action="store_true",
+                    help="with --top: ClusterIndex.search_deep, the same result for up to 2048 rows per query")
     sp.add_argument("--radius", type=float, metavar="R",
                     help="in place of --top: every row within R of each query (with --squared, R is the squared "
                          "radius); writes lims, rows and distances")

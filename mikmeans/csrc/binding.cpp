@@ -393,6 +393,60 @@ void ivf_range(const Tensor& Q, const Tensor& qn, const Tensor& r2, const Tensor
   hip_check(mk::launch_ivf_range(dtype_of(Q), (int)dpad, (int)P, fill, a, stream()), "ivf_range");
 }
 
+// Deep search (csrc/deep.hip): one radix-select pass's histogram over the walk ...
+void ivf_hist(const Tensor& Q, const Tensor& qn, const Tensor& pack, const Tensor& cn, const Tensor& offsets,
+              const Tensor& toff, const Tensor& order, const Tensor& porder, const Tensor& poff, const Tensor& icum,
+              int64_t nprobe, int64_t dpad, int64_t P, int64_t max_items, const Tensor& table,
+              const c10::optional<Tensor>& prefix, int64_t pass) {
+  TORCH_CHECK(pass >= 0 && pass < mk::QUANTILE_PASSES, "mikmeans: ivf_hist pass must be 0..3, got ", pass);
+  const bool has_prefix = prefix.has_value() && prefix->defined();
+  mk::IvfHistArgs a;
+  a.w = check_walk("ivf_hist", Q, qn, pack, cn, offsets, toff, order, porder, poff, icum, nprobe, dpad, P, max_items,
+                   [&](int dt, int64_t npairs) {
+                     const int64_t nq = Q.size(0);
+                     TORCH_CHECK(table.dim() == 2 && table.size(0) == nq && table.size(1) == mk::QUANTILE_BINS,
+                                 "mikmeans: ivf_hist's table must be [nq, 256]");
+                     check_i32(table, "table", nq * mk::QUANTILE_BINS);
+                     TORCH_CHECK(table.get_device() == Q.get_device(), "mikmeans: table and Q must share a device");
+                     TORCH_CHECK(pass == 0 || has_prefix, "mikmeans: ivf_hist's passes 1..3 take a prefix");
+                     if (has_prefix) {
+                       check_i32(*prefix, "prefix", nq);
+                       TORCH_CHECK(prefix->get_device() == Q.get_device(),
+                                   "mikmeans: prefix and Q must share a device");
+                     }
+                     return mk::ivf_hist_blocks(dt, (int)dpad, npairs);
+                   });
+  a.pass = (int)pass;
+  a.prefix = has_prefix ? prefix->data_ptr<int32_t>() : nullptr;
+  a.table = reinterpret_cast<uint32_t*>(table.data_ptr<int32_t>());
+  hip_check(mk::launch_ivf_hist(dtype_of(Q), (int)dpad, (int)P, a, stream()), "ivf_hist");
+}
+
+// ... and its select: per query the bin that holds the remaining rank
+void ivf_select(const Tensor& table, const Tensor& prefix, const Tensor& rank, const Tensor& hits, const Tensor& cand,
+                int64_t m, int64_t pass) {
+  TORCH_CHECK(pass >= 0 && pass < mk::QUANTILE_PASSES, "mikmeans: ivf_select pass must be 0..3, got ", pass);
+  TORCH_CHECK(m >= 1 && m <= mk::IVF_DEEP_MAX_M, "mikmeans: ivf_select needs 1 <= m <= ", mk::IVF_DEEP_MAX_M,
+              ", got m = ", m);
+  TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUANTILE_BINS, "mikmeans: ivf_select's table must be [nq, 256]");
+  const int64_t nq = table.size(0);
+  TORCH_CHECK(nq <= INT32_MAX, "mikmeans: too many queries");
+  check_i32(table, "table", nq * mk::QUANTILE_BINS);
+  check_i32(prefix, "prefix", nq);
+  check_i64(rank, "rank", nq);
+  check_i64(hits, "hits", nq);
+  check_i64(cand, "cand", nq);
+  const int dev = table.get_device();
+  TORCH_CHECK(prefix.get_device() == dev && rank.get_device() == dev && hits.get_device() == dev &&
+                  cand.get_device() == dev,
+              "mikmeans: table, prefix, rank, hits and cand must share a device");
+  mk::IvfSelectArgs a;
+  a.table = reinterpret_cast<const uint32_t*>(table.data_ptr<int32_t>());
+  a.prefix = prefix.data_ptr<int32_t>(); a.rank = rank.data_ptr<int64_t>(); a.hits = hits.data_ptr<int64_t>();
+  a.cand = cand.data_ptr<int64_t>(); a.nq = nq; a.m = (int)m; a.pass = (int)pass;
+  hip_check(mk::launch_ivf_select(a, stream()), "ivf_select");
+}
+
 void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {
   TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUALITY_WORDS, "mikmeans: table must be [K, ",
               mk::QUALITY_WORDS, "]");
@@ -1141,6 +1195,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("P"), py::arg("max_items"), py::arg("counts"), py::arg("base") = py::none(),
         py::arg("keys") = py::none());
   m.def("ivf_range_blocks", &mk::ivf_range_blocks);
+  m.def("ivf_hist", &ivf_hist,
+        "one radix-select pass of a deep search: every row of every (query, probed list) pair added into the query's "
+        "256-bin histogram of its d2 bits' digit (u32 as int32 [nq, 256], integer atomics)",
+        py::arg("Q"), py::arg("qn"), py::arg("pack"), py::arg("cn"), py::arg("offsets"), py::arg("toff"),
+        py::arg("order"), py::arg("porder"), py::arg("poff"), py::arg("icum"), py::arg("nprobe"), py::arg("dpad"),
+        py::arg("P"), py::arg("max_items"), py::arg("table"), py::arg("prefix") = py::none(), py::arg("pass") = 0);
+  m.def("ivf_hist_blocks", &mk::ivf_hist_blocks);
+  m.def("ivf_select", &ivf_select,
+        "per query: the bin of the histogram that holds the remaining rank; updates prefix, rank, hits (and cand in "
+        "pass 0)",
+        py::arg("table"), py::arg("prefix"), py::arg("rank"), py::arg("hits"), py::arg("cand"), py::arg("m"),
+        py::arg("pass"));
+  m.attr("IVF_DEEP_MAX_M") = mk::IVF_DEEP_MAX_M;
   m.def("quality_accumulate", &quality_accumulate,
         "add the top-2 output's per-cluster quality words into table [K, QUALITY_WORDS] (integer atomics)",
         py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("path") = -1);

@@ -228,6 +228,37 @@ struct IvfRangeArgs {
 int ivf_range_blocks(int dtype, int dpad, int64_t npairs);
 hipError_t launch_ivf_range(int dtype, int dpad, int P, bool fill, const IvfRangeArgs& a, hipStream_t s);
 
+// ---- deep search: the m-th smallest d2 of every query by radix select (csrc/deep.hip) -------
+// A most-significant-digit radix select over bits(d2) of the rows of a query's probed lists, on
+// the walk's work items (P from ivf_hist_blocks) and with the scan's d2: up to four passes of
+// 8-bit digits (shift s = 24 - 8 pass), each a histogram over the walk and a select.
+// Histogram: every row k < list length of every pair adds one to table[q][bits >> 24] (pass 0) or,
+// where bits >> (s + 8) == prefix[q] >> (s + 8), to table[q][(bits >> s) & 255] (passes 1..3).  No
+// finiteness filter: an inf or NaN d2 counts (top byte <= 0x7f).  The table (u32 [nq, 256],
+// zeroed by the caller) is only ever added into with integer atomics: the same on every launch.
+struct IvfHistArgs {
+  IvfWalkArgs w;
+  int pass;                  // 0..3
+  const int32_t* prefix;     // [nq] the bits fixed so far (passes 1..3)
+  uint32_t* table;           // [nq, 256]
+};
+int ivf_hist_blocks(int dtype, int dpad, int64_t npairs);
+hipError_t launch_ivf_hist(int dtype, int dpad, int P, const IvfHistArgs& a, hipStream_t s);
+// Select, one workgroup a query.  Pass 0: cand[q] = the sum of the bins, R = min(m, cand) - 1;
+// later passes R = rank[q].  b = the smallest bin whose running count exceeds R: prefix |= b << s,
+// rank = R - the count below b, hits[q] = the rows with bits <= prefix | (2^s - 1), which is
+// min(m, cand) - 1 - rank + count[b].  cand = 0: prefix, rank and hits 0.  1 <= m <= IVF_DEEP_MAX_M.
+constexpr int IVF_DEEP_MAX_M = 2048;
+struct IvfSelectArgs {
+  const uint32_t* table;     // [nq, 256]
+  int32_t* prefix;           // [nq] in (passes 1..3) / out
+  int64_t* rank;             // [nq] in (passes 1..3) / out
+  int64_t* hits;             // [nq] out
+  int64_t* cand;             // [nq] out (pass 0) / in
+  int64_t nq; int m; int pass;
+};
+hipError_t launch_ivf_select(const IvfSelectArgs& a, hipStream_t s);
+
 // ---- per-cluster quality table (csrc/quality.hip) ----------------------------------------
 // Folds launch_topk's output (m = 1 or 2) into table[K][QUALITY_WORDS] (u64, only ever added
 // into) with integer atomics: per label the digits of sum a^2 and the row count, the digits of

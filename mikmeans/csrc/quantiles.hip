@@ -57,6 +57,7 @@
 // order give a wave nothing to share and two rounds cost under 1 %; rows ordered by label put
 // every wave on one cluster, and two rounds take pass 0 from 0.74 to 0.045 ms at K = 1024
 // (QUANTILE_AGG_ROUNDS = 2; more rounds only add to the later passes, whose digits differ).
+#include "bins.h"
 #include "common.h"
 #include "fold.h"
 #include "kernels.h"
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(FOLD_LDS_THREADS) void quantile_hist_lds_kernel(Qua
 // that holds rank R.
 __global__ __launch_bounds__(QUANTILE_BINS) void quantile_select_kernel(QuantileSelectArgs a) {
   __shared__ unsigned long long wsum[QUANTILE_BINS / 64];
-  const int k = blockIdx.x, b = threadIdx.x, lane = b & 63, w = b >> 6;
+  const int k = blockIdx.x, b = threadIdx.x;
   const int s = 24 - 8 * a.pass;
   unsigned long long c = 0, incl = 0, total = 0;
   for (int j = 0; j < a.Q; ++j) {
@@ -156,22 +157,7 @@ __global__ __launch_bounds__(QUANTILE_BINS) void quantile_select_kernel(Quantile
     int64_t R = a.pass ? a.rank[pair] : 0;
     if (a.pass > 0 || j == 0) {
       c = a.table[(a.pass ? pair : (int64_t)k) * QUANTILE_BINS + b];
-      incl = c;
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long v = __shfl_up(incl, o);
-        if (lane >= o) incl += v;
-      }
-      __syncthreads();                       // (the previous pair's wsum has been read)
-      if (lane == 63) wsum[w] = incl;
-      __syncthreads();
-      unsigned long long below = 0;
-      total = 0;
-      for (int i = 0; i < QUANTILE_BINS / 64; ++i) {
-        const unsigned long long v = wsum[i];
-        if (i < w) below += v;
-        total += v;
-      }
-      incl += below;
+      bins_running_count(c, wsum, incl, total);
     }
     if (a.pass == 0) {
       const int64_t n = (int64_t)total;

@@ -27,17 +27,6 @@
 
 namespace mk {
 
-// Whether a wave's queries stay in registers (4 NQ VGPRs a block); past that (f32 D > 768) the
-// fragments are fetched again for every tile, as in topk.h
-constexpr bool range_xreg(int nq) { return nq <= 48; }
-
-// Pair blocks per wave: the queries' fragments (4 NQ VGPRs), the accumulators (4) and the
-// per-block state (pair id, base, radius, count: ~8) of every block within ~176 VGPRs, at most 4
-constexpr int range_blocks(int nq) {
-  const int p = 176 / (4 * nq + 12);
-  return p < 1 ? 1 : (p > 4 ? 4 : p);
-}
-
 template <typename T, int DPAD, int P, bool FILL>
 __global__ __launch_bounds__(TK_NW * 64, 2) void ivf_range_kernel(IvfRangeArgs a) {
   constexpr int V = Elem<T>::V;

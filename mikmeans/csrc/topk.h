@@ -30,6 +30,18 @@ constexpr int topk_blocks(int nq, int m) {
   return p < 1 ? 1 : (p > 4 ? 4 : p);
 }
 
+// The walks without a list (csrc/range.hip, csrc/deep.hip).
+// Whether a wave's queries stay in registers (4 NQ VGPRs a block); past that (f32 D > 768) the
+// fragments are fetched again for every tile, as in topk.h
+constexpr bool range_xreg(int nq) { return nq <= 48; }
+
+// Pair blocks per wave: the queries' fragments (4 NQ VGPRs), the accumulators (4) and the
+// per-block state (pair id, base, radius, count: ~8) of every block within ~176 VGPRs, at most 4
+constexpr int range_blocks(int nq) {
+  const int p = 176 / (4 * nq + 12);
+  return p < 1 ? 1 : (p > 4 ? 4 : p);
+}
+
 // Candidate (c, ck) into a lane's sorted list (the caller has skipped it where no lane of the
 // wave has c < bv[M - 1]): slot j takes its left neighbour where c goes in front of both, c
 // itself where it goes in front of slot j only (every compare against c: a displaced entry

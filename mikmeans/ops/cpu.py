@@ -414,3 +414,66 @@ def index_range(index, Q: torch.Tensor, centers: torch.Tensor, r2: torch.Tensor,
     if want_probe:
         return lims, keys, (torch.cat(ranks) if ranks else empty)
     return lims, keys
+
+
+INDEX_DEEP_MAX_M = 2048             # csrc/kernels.h IVF_DEEP_MAX_M: the longest deep-search result
+
+
+def index_pair_bits(index, Q: torch.Tensor, probes: torch.Tensor):
+    """What a deep search ranks, in the arithmetic of :func:`index_search`: ``(bits int64 [nq, nv],
+    member bool [nq, nv], rid int64 [nv])`` -- the bit pattern of every query's ``d2`` against every
+    indexed row (in list order), whether the row's list is one of the query's ``probes`` (int
+    [nq, nprobe]) and the rows' ids."""
+    lid, rid, c, cn = _index_rows(index, Q.shape[1])
+    bits = _block_d2(Q, c, cn).contiguous().view(torch.int32).to(torch.int64)
+    member = torch.zeros((Q.shape[0], index.K), dtype=torch.bool, device=Q.device)
+    member.scatter_(1, probes.to(torch.int64), True)
+    return bits, member[:, lid], rid
+
+
+def index_hist(bits: torch.Tensor, member: torch.Tensor, prefix: torch.Tensor | None, pass_: int) -> torch.Tensor:
+    """One radix-select pass's histogram of a deep search (csrc/deep.hip ivf_hist_kernel in integer
+    torch arithmetic): int64 ``[nq, 256]``.  ``bits`` int64 ``[nq, nc]``: the bit patterns of every
+    query's clamped ``d2`` against ``nc`` candidate rows; ``member`` bool ``[nq, nc]``: the rows
+    that count for the query (those of its probed lists).  Pass 0: a row adds one to
+    ``(q, bits >> 24)``; passes 1..3 (``prefix`` int32 ``[nq]``): to ``(q, (bits >> s) & 255)`` where
+    ``bits >> (s + 8) == prefix[q] >> (s + 8)``, ``s = 24 - 8 * pass``.  No finiteness filter."""
+    pass_ = int(pass_)
+    if not 0 <= pass_ < QUANTILE_PASSES:
+        raise ValueError(f"index_hist needs a pass in 0..3, got {pass_}")
+    if pass_ and (prefix is None or prefix.shape != bits.shape[:1]):
+        raise ValueError("index_hist needs a prefix [nq] in passes 1..3")
+    nq, s = bits.shape[0], 24 - 8 * pass_
+    ok = member
+    if pass_:
+        ok = ok & ((bits >> (s + 8)) == ((prefix.to(torch.int64) & 0xFFFFFFFF) >> (s + 8))[:, None])
+    slot = torch.arange(nq, dtype=torch.int64, device=bits.device)[:, None] * QUANTILE_BINS + ((bits >> s) & 255)
+    return torch.bincount(slot[ok], minlength=nq * QUANTILE_BINS).view(nq, QUANTILE_BINS)
+
+
+def index_select(table: torch.Tensor, prefix: torch.Tensor, rank: torch.Tensor, cand: torch.Tensor, m: int, pass_: int):
+    """One select step of a deep search on a histogram int64 ``[nq, 256]`` (csrc/deep.hip
+    ivf_select_kernel): ``(prefix int32 [nq], rank int64 [nq], hits int64 [nq], cand int64 [nq])``.
+    Pass 0 (``prefix``, ``rank`` and ``cand`` are not read): ``cand`` = the sum of the bins and
+    R = min(m, cand) - 1; later passes R = ``rank``.  b = the smallest bin whose running count
+    exceeds R: prefix |= b << s, rank = R - the count below b and hits = the candidates with
+    ``bits <= prefix | (2^s - 1)`` = min(m, cand) - 1 - rank + count[b].  ``cand`` = 0: all zeros."""
+    pass_, m = int(pass_), int(m)
+    s = 24 - 8 * pass_
+    if pass_ == 0:
+        cand = table.sum(1)
+        P = torch.zeros_like(cand)
+    else:
+        P = prefix.to(torch.int64) & 0xFFFFFFFF
+    found = cand.clamp(max=m)
+    R = found - 1 if pass_ == 0 else rank.to(torch.int64)
+    cum = table.cumsum(1)
+    over = cum > R[:, None]
+    has = over.any(1) & (cand > 0)                           # (false only where cand = 0)
+    b = over.to(torch.int8).argmax(1)
+    below = (cum - table).gather(1, b[:, None])[:, 0]
+    zero = torch.zeros_like(R)
+    P = torch.where(has, P | (b << s), zero)
+    R = torch.where(has, R - below, zero)
+    hits = torch.where(has, found - 1 - R + table.gather(1, b[:, None])[:, 0], zero)
+    return P.to(torch.int32), R, hits, cand

@@ -9,6 +9,9 @@
   the per-query merge: sorted ``(d2 bits << 32 | row)`` keys
 * :func:`index_range`   every row of those lists within a radius of the query (csrc/range.hip: a count
   pass, a cumulative sum and a fill pass): ``(lims, keys)``, a variable number of keys per query
+* :func:`index_search_deep`  :func:`index_search` for up to 2048 rows a query: a radix select over the
+  ``d2`` bits (csrc/deep.hip: :func:`index_hist` / :func:`index_select`) finds every query's m-th
+  distance, the range passes collect the rows under it
 * :func:`index_decode`  keys to ``(rows, squared distances)``
 
 GPU tensors of up to 1024 features run the native kernels; CPU tensors and wider rows run the
@@ -24,12 +27,19 @@ from .native import dpad_for, dtype_code, require
 
 __all__ = ["PARTITION_MAX_K", "IVF_EMPTY_KEY", "INDEX_MAX_M", "INDEX_SCAN_KEYS", "partition", "RowIndex",
            "index_tiles", "pair_items", "index_build", "index_add", "index_remove", "index_search", "index_range",
-           "index_decode"]
+           "index_decode", "INDEX_DEEP_MAX_M", "INDEX_DEEP_OVERSHOOT", "deep_block_queries", "index_hist",
+           "index_select", "index_search_deep"]
 
 PARTITION_MAX_K = cpu.PARTITION_MAX_K   # csrc/kernels.h (the extension exports the same number)
 IVF_EMPTY_KEY = cpu.IVF_EMPTY_KEY       # a result slot without a row: behind every key
 INDEX_MAX_M = TOPK_NATIVE_MAX           # the scan kernel's longest list (TOPK_MAX)
 INDEX_SCAN_KEYS = 1 << 27               # keys (8 B each) one scan launch may write: queries go in blocks
+INDEX_DEEP_MAX_M = cpu.INDEX_DEEP_MAX_M  # the longest deep-search result (csrc/kernels.h IVF_DEEP_MAX_M)
+# A deep search stops selecting digits once its radius lets through at most this many times the
+# rows wanted, summed over the block: one more histogram walk against fill and sort volume
+# (docs/SEARCH_DEEP.md has the measurement).  The result does not depend on it.
+INDEX_DEEP_OVERSHOOT = 2
+QUANTILE_BINS = cpu.QUANTILE_BINS
 
 
 def partition(labels: torch.Tensor, K: int, *, want_pos: bool = False):
@@ -379,6 +389,131 @@ def index_range(index: RowIndex, Q: torch.Tensor, centers: torch.Tensor, r2, npr
     if want_probe:
         return lims, keys, (torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev))
     return lims, keys
+
+
+def deep_block_queries(m: int, nprobe: int) -> int:
+    """Queries per block of a deep search: the histogram (1 KiB a query), the pair arrays (porder,
+    probes, counts and base: 28 B a pair) and ``INDEX_DEEP_OVERSHOOT * m`` keys a query within
+    ``INDEX_SCAN_KEYS`` keys' worth of bytes."""
+    per = 4 * QUANTILE_BINS + 28 * int(nprobe) + 8 * INDEX_DEEP_OVERSHOOT * int(m)
+    return max(1, 8 * INDEX_SCAN_KEYS // per)
+
+
+def index_hist(index: RowIndex, Q: torch.Tensor, probes: torch.Tensor, pass_: int, prefix: torch.Tensor | None = None,
+               *, table: torch.Tensor | None = None, P: int | None = None, walk: tuple | None = None) -> torch.Tensor:
+    """One radix-select pass's histogram of a deep search (csrc/deep.hip): every row of the lists
+    ``probes`` (int [nq, nprobe]) names for a query adds one to the query's 256 bins by a digit of
+    its ``d2`` bits -- ``bits >> 24`` in pass 0; ``(bits >> s) & 255``, ``s = 24 - 8 * pass``, where
+    ``bits >> (s + 8)`` is ``prefix[q]``'s (int32 [nq]) in passes 1..3.  Rows at an infinite or NaN
+    distance count too.  Native: u32 counts as int32 ``[nq, 256]``, added into ``table`` where one is
+    given (else a zeroed one); ``P``: pair blocks a wave (``ivf_hist_blocks`` or 1: the same table);
+    ``walk``: the walk's arguments where the caller holds them (``_walk_args`` at ``P``).  A CPU index
+    runs :func:`mikmeans.ops.cpu.index_hist` (int64)."""
+    Qp = _check_queries("search", index, Q, probes.shape[1])
+    if not index.native:
+        bits, member, _ = cpu.index_pair_bits(index, Qp, probes)
+        return cpu.index_hist(bits, member, prefix, pass_)
+    C = require()
+    if walk is None:
+        P = int(P) if P else C.ivf_hist_blocks(dtype_code(Qp.dtype), index.cols, probes.numel())
+        walk = _walk_args(index, Qp, probes, P)
+    if table is None:
+        table = torch.zeros((Qp.shape[0], QUANTILE_BINS), dtype=torch.int32, device=Qp.device)
+    C.ivf_hist(*walk, table, prefix if int(pass_) else None, int(pass_))
+    return table
+
+
+def index_select(table: torch.Tensor, prefix: torch.Tensor, rank: torch.Tensor, hits: torch.Tensor,
+                 cand: torch.Tensor, m: int, pass_: int) -> None:
+    """One select step of a deep search, in place (csrc/deep.hip; :func:`mikmeans.ops.cpu.index_select`
+    has the rule): ``prefix`` int32, ``rank`` / ``hits`` / ``cand`` int64, all ``[nq]``."""
+    if table.is_cuda:
+        require().ivf_select(table, prefix, rank, hits, cand, int(m), int(pass_))
+        return
+    for dst, src in zip((prefix, rank, hits, cand), cpu.index_select(table, prefix, rank, cand, m, pass_)):
+        dst.copy_(src)
+
+
+def _deep_radius(index: RowIndex, Qp: torch.Tensor, probes: torch.Tensor, m: int, passes: int | None):
+    """``(r2 float32 [nq], passes run)`` of one block of queries (native): the radix select's prefix
+    after the last pass run with every lower bit set, as a float32 bit pattern -- at least every
+    query's ``min(m, candidates)``-th smallest ``d2``, and exactly it after four passes.  It may be
+    an inf or NaN pattern: it is formed by integer ops and only ever compared as bits."""
+    C = require()
+    nq, dev = Qp.shape[0], Qp.device
+    P = C.ivf_hist_blocks(dtype_code(Qp.dtype), index.cols, probes.numel())
+    walk = _walk_args(index, Qp, probes, P)
+    table = torch.empty((nq, QUANTILE_BINS), dtype=torch.int32, device=dev)
+    prefix = torch.zeros(nq, dtype=torch.int32, device=dev)
+    rank, hits, cand = (torch.zeros(nq, dtype=torch.int64, device=dev) for _ in range(3))
+    for p in range(cpu.QUANTILE_PASSES):
+        table.zero_()
+        index_hist(index, Qp, probes, p, prefix, table=table, walk=walk)
+        index_select(table, prefix, rank, hits, cand, m, p)
+        if p + 1 == (passes or cpu.QUANTILE_PASSES):
+            break
+        # (the one host read of the pass: one more walk against the fill and sort volume)
+        if passes is None and bool(hits.sum() <= INDEX_DEEP_OVERSHOOT * cand.clamp(max=m).sum()):
+            break
+    return (prefix | ((1 << (24 - 8 * p)) - 1)).view(torch.float32), p + 1
+
+
+def _deep_collect(index: RowIndex, Qp: torch.Tensor, probes: torch.Tensor, r2: torch.Tensor, m: int) -> torch.Tensor:
+    """Sorted keys int64 [nq, m] of one block of queries (native) from a radius that lets at least
+    every query's ``min(m, candidates)`` nearest rows through: the range passes' count, cumulative
+    sum and fill, the sort by unique keys and every query's first ``m``."""
+    nq, dev = Qp.shape[0], Qp.device
+    counts, kb = _range_block(index, Qp, probes, r2, False)
+    cq = counts.view(nq, -1).sum(1)
+    qid = torch.repeat_interleave(torch.arange(nq, device=dev), cq, output_size=kb.numel())
+    kb, o1 = kb.sort()                                        # unique keys: any sort gives one order
+    o2 = qid[o1].sort(stable=True).indices
+    kb, qid = kb[o2], qid[o1][o2]
+    pos = torch.arange(kb.numel(), device=dev) - (torch.cumsum(cq, 0) - cq)[qid]
+    keep = pos < m
+    keys = torch.full((nq, m), IVF_EMPTY_KEY, dtype=torch.int64, device=dev)
+    keys[qid[keep], pos[keep]] = kb[keep]
+    return keys
+
+
+def index_search_deep(index: RowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: int, *, pack=None,
+                      passes: int | None = None, block_queries: int | None = None) -> torch.Tensor:
+    """:func:`index_search` past the scan kernel's list: the ``m`` nearest indexed rows of every query
+    among the lists of its ``nprobe`` nearest centres for ``1 <= m <= INDEX_DEEP_MAX_M`` -- the same
+    int64 keys ``[nq, m]``, ``d2 bits << 32 | row`` ascending, ``IVF_EMPTY_KEY`` where the lists hold
+    fewer rows, and for ``m <= INDEX_MAX_M`` :func:`index_search`'s bit for bit.
+
+    No candidate list is kept.  A most-significant-digit radix select over the ``d2`` bits
+    (csrc/deep.hip: a histogram pass over the walk and a select per 8-bit digit, csrc/quantiles.hip's
+    method) finds a radius that is at least every query's m-th smallest ``d2`` -- after four passes
+    exactly it -- and the range passes (csrc/range.hip) collect the rows under it; each query keeps
+    the first ``m`` of its sorted keys.  The loop stops after any pass where the radius lets through
+    at most ``INDEX_DEEP_OVERSHOOT`` times the rows wanted over the block (one scalar host read a
+    pass): one more walk is traded against fill and sort volume, and the result does not depend on
+    it.  ``passes`` = 1..4 forces the pass count.  Rows at the m-th distance are all under the exact
+    radius: ties there make the rows collected exceed ``m`` by the number of tied rows (the lower row
+    ids are kept), which is inherent to the method.  Queries go through in blocks
+    (:func:`deep_block_queries`, or ``block_queries``); the result does not depend on the blocking
+    and is bitwise the same from run to run.  A CPU index runs the mirror of :func:`index_search`."""
+    m, nprobe = int(m), int(nprobe)
+    if not 1 <= m <= INDEX_DEEP_MAX_M:
+        raise ValueError(f"search_deep needs 1 <= m <= {INDEX_DEEP_MAX_M}, got m = {m}")
+    if passes is not None and not 1 <= int(passes) <= cpu.QUANTILE_PASSES:
+        raise ValueError(f"search_deep needs passes in 1..{cpu.QUANTILE_PASSES} (or None), got {passes}")
+    if Q.dim() != 2:
+        raise ValueError(f"search_deep needs queries [nq, D], got shape {tuple(Q.shape)}")
+    Qp = _check_queries("search_deep", index, Q, nprobe)
+    nq = Qp.shape[0]
+    if not index.native:
+        return cpu.index_search(index, Qp, centers, m, nprobe)
+    keys = torch.empty((nq, m), dtype=torch.int64, device=Qp.device)
+    block = max(1, int(block_queries)) if block_queries else deep_block_queries(m, nprobe)
+    for s in range(0, nq, block):
+        Qb = Qp[s : s + block]
+        probes, _ = topk(Qb, centers, nprobe, pack=pack)
+        r2, _ = _deep_radius(index, Qb, probes, m, None if passes is None else int(passes))
+        keys[s : s + block] = _deep_collect(index, Qb, probes, r2, m)
+    return keys
 
 
 def index_decode(keys: torch.Tensor, *, row_start: int = 0):

@@ -501,6 +501,43 @@ def plan_index_update(n_old: int, n_total: int, D: int, K: int, dtype="bfloat16"
     return MemoryPlan("index-update", n_total, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
 
 
+INDEX_SCAN_KEYS = 1 << 27        # ops.INDEX_SCAN_KEYS
+INDEX_DEEP_OVERSHOOT = 2         # ops.INDEX_DEEP_OVERSHOOT
+DEEP_BINS = 256                  # one 8-bit digit
+
+
+def deep_block_queries(m: int, nprobe: int) -> int:
+    """ops.deep_block_queries: queries per block of a deep search."""
+    return max(1, 8 * INDEX_SCAN_KEYS // (4 * DEEP_BINS + 28 * int(nprobe) + 8 * INDEX_DEEP_OVERSHOOT * int(m)))
+
+
+def plan_index_search_deep(n: int, D: int, K: int, dtype="bfloat16", *, nq: int, m: int, nprobe: int) -> MemoryPlan:
+    """A deep search (ops.index_search_deep) of ``nq`` queries for ``m`` rows each over ``nprobe``
+    lists of an index of ``n`` ids: the index and the result, and per block of queries the two
+    phases' scratch -- the radix select's histogram (1 KiB a query), its per-query state and the
+    walk's pair arrays; then the range passes' counts and bases and the keys under the radius
+    (``INDEX_DEEP_OVERSHOOT * m`` a query where the stop rule holds; rows tied at the m-th place and
+    a forced pass count can exceed it) with the sort's copies of them."""
+    es = esize_of(dtype)
+    Dp = padded_cols(D, es)
+    cols = dpad_for(Dp, es) or Dp
+    rows = index_tiles(n, K) * 16
+    p = {"row_pack": _r(rows * cols * es), "cn": _r(rows * 4), "order": _r(n * 8), "offsets": _r((K + 1) * 8),
+         "tile_offsets": _r((K + 1) * 8), "result_keys": _r(nq * m * 8)}
+    B = min(int(nq), deep_block_queries(m, nprobe))
+    pairs = B * int(nprobe)
+    walk = {"queries": _r(B * Dp * es), "query_norms": _r(B * 4), "probes": _r(pairs * 4), "probe_d2": _r(pairs * 4),
+            "pair_order": _r(pairs * 8), "pair_offsets": _r((K + 1) * 8), "item_cum": _r((K + 1) * 8),
+            "partition_cells": _r(K * partition_blocks(pairs, K) * 8)}
+    keys = _r(INDEX_DEEP_OVERSHOOT * m * B * 8)
+    tr = {"select": {**walk, "histogram": _r(B * DEEP_BINS * 4), "prefix": _r(B * 4), "rank": _r(B * 8),
+                     "hits": _r(B * 8), "candidates": _r(B * 8)},
+          "collect": {**walk, "radius": _r(B * 4), "pair_counts": _r(pairs * 8), "pair_base": _r(2 * pairs * 8),
+                      "keys": keys, "sorted_keys": keys, "sort_order": keys, "query_ids": keys, "query_order": keys,
+                      "block_keys": _r(B * m * 8)}}
+    return MemoryPlan("index-search-deep", n, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
+
+
 # ------------------------------------------------------------------------ budget
 def hbm_budget(device=None) -> int:
     """Bytes a fit on ``device`` may allocate: ``MIKMEANS_HBM_BYTES`` when set, else the free
