@@ -545,13 +545,43 @@ void quantile_select(const Tensor& table, const Tensor& q, const Tensor& prefix,
   hip_check(mk::launch_quantile_select(a, stream()), "quantile_select");
 }
 
+// The M-step argument block update and update_delta (delta) share, checked: the points (n logical
+// rows, n < 0: every row of X), their labels, the slabs of n_chunks chunks (one for the global
+// fallback, slice width sw = 0, a multiple of 8 otherwise), the weights and the exponents.
+mk::UpdateArgs update_args(const Tensor& X, int dt, int64_t n, bool delta, int& sw, const Tensor& labels,
+                           int64_t K, const Tensor& slab, const Tensor& cnt_slab, int64_t n_chunks,
+                           const c10::optional<Tensor>& weights, const Tensor& col_exp, int64_t cnt_exp) {
+  mk::UpdateArgs a;
+  a.ldx = check_points(X, dt);
+  const int64_t N = n < 0 ? X.size(0) : n;
+  a.X = X.data_ptr(); a.N = N; a.D = (int)X.size(1);
+  check_i32(labels, "labels", N);
+  sw = mk::update_slice_width(dt, (int)K, a.D, delta || weights.has_value());
+  TORCH_CHECK(!delta || sw > 0, "mikmeans: incremental M-step needs an LDS slice (K too large)");
+  TORCH_CHECK(sw == 0 ? n_chunks == 1 : n_chunks % 8 == 0, "mikmeans: bad n_chunks");
+  check_i64(slab, "slab", n_chunks * K * a.D);
+  check_i64(cnt_slab, "cnt_slab", n_chunks * K);
+  if (weights.has_value()) check_f32(*weights, "weights", N);
+  check_i32(col_exp, "col_exp", a.D);
+  a.labels = labels.data_ptr<int32_t>(); a.K = (int)K; a.n_chunks = (int)n_chunks;
+  a.slab = (long long*)slab.data_ptr<int64_t>(); a.cnt_slab = (long long*)cnt_slab.data_ptr<int64_t>();
+  a.weights = opt_ptr<const float>(weights);
+  a.col_exp = col_exp.data_ptr<int32_t>(); a.cnt_exp = (int)cnt_exp; a.clamp = 0;
+  return a;
+}
+// The changed-row list of the incremental M-step
+void check_delta_list(const Tensor& list) {
+  check_cuda(list, "list");
+  TORCH_CHECK(list.scalar_type() == at::kInt && list.dim() == 2 && list.size(1) == 2 && list.is_contiguous(),
+              "mikmeans: list must be contiguous int32 [cap, 2]");
+}
+
 void update(const Tensor& X, const Tensor& labels, int64_t K, const Tensor& slab,
             const Tensor& cnt_slab, int64_t n_chunks, const c10::optional<Tensor>& weights,
             const Tensor& col_exp, int64_t cnt_exp, bool clamp,
             const c10::optional<Tensor>& clamp_count, const c10::optional<Tensor>& col_exp2,
             const c10::optional<Tensor>& rows) {
   const int dt = dtype_of(X);
-  const int64_t ldx = check_points(X, dt);
   const bool gathered = rows.has_value() && rows->defined();
   if (gathered) {
     check_i64(*rows, "rows", 0);
@@ -559,33 +589,21 @@ void update(const Tensor& X, const Tensor& labels, int64_t K, const Tensor& slab
                 "mikmeans: gathered rows take plain (bounded) M-step passes");
     TORCH_CHECK(X.size(0) > 0 || rows->numel() == 0, "mikmeans: gathered rows from an empty X");
   }
-  const int64_t N = gathered ? rows->numel() : X.size(0);
-  const int D = (int)X.size(1);
-  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kInt && labels.numel() >= N,
-              "mikmeans: labels must be int32 [N]");
-  const int sw = mk::update_slice_width(dt, (int)K, D, weights.has_value());
-  TORCH_CHECK(sw == 0 ? n_chunks == 1 : n_chunks % 8 == 0, "mikmeans: bad n_chunks");
-  check_i64(slab, "slab", n_chunks * K * D);
-  check_i64(cnt_slab, "cnt_slab", n_chunks * K);
-  if (weights.has_value()) check_f32(*weights, "weights", N);
-  check_i32(col_exp, "col_exp", D);
+  int sw;
+  mk::UpdateArgs a = update_args(X, dt, gathered ? rows->numel() : -1, false, sw, labels, K, slab, cnt_slab,
+                                 n_chunks, weights, col_exp, cnt_exp);
   if (sw == 0) {  // global-atomic fallback accumulates into zeroed buffers
-    hip_check(hipMemsetAsync(slab.data_ptr(), 0, K * D * 8, stream()), "memset");
+    hip_check(hipMemsetAsync(slab.data_ptr(), 0, K * a.D * 8, stream()), "memset");
     hip_check(hipMemsetAsync(cnt_slab.data_ptr(), 0, K * 8, stream()), "memset");
   }
-  mk::UpdateArgs a;
-  a.X = X.data_ptr(); a.N = N; a.D = D; a.ldx = ldx;
-  a.labels = labels.data_ptr<int32_t>(); a.K = (int)K; a.n_chunks = (int)n_chunks;
-  a.slab = (long long*)slab.data_ptr<int64_t>(); a.cnt_slab = (long long*)cnt_slab.data_ptr<int64_t>();
-  a.weights = opt_ptr<const float>(weights);
-  a.col_exp = col_exp.data_ptr<int32_t>(); a.cnt_exp = (int)cnt_exp; a.clamp = clamp ? 1 : 0;
+  a.clamp = clamp ? 1 : 0;
   if (clamp_count.has_value()) {
     check_i32(*clamp_count, "clamp_count", 1);
     a.clamp_count = clamp_count->data_ptr<int32_t>();
   }
   if (col_exp2.has_value()) {
     TORCH_CHECK(sw > 0 && !clamp, "mikmeans: the residual pass needs the LDS path and no clamp");
-    check_i32(*col_exp2, "col_exp2", D);
+    check_i32(*col_exp2, "col_exp2", a.D);
     a.col_exp2 = col_exp2->data_ptr<int32_t>();
   }
   if (gathered) a.rows = rows->data_ptr<int64_t>();
@@ -602,9 +620,7 @@ void label_delta_rows(const Tensor& labels, const Tensor& prev, const Tensor& ro
   check_i64(rows, "rows", 0);
   check_i64(rcount, "rcount", 1);
   TORCH_CHECK(rows.numel() <= N, "mikmeans: more candidate rows than labels");
-  check_cuda(list, "list");
-  TORCH_CHECK(list.scalar_type() == at::kInt && list.dim() == 2 && list.size(1) == 2 && list.is_contiguous(),
-              "mikmeans: list must be contiguous int32 [cap, 2]");
+  check_delta_list(list);
   TORCH_CHECK(N < ((int64_t)1 << 31) && list.size(0) < ((int64_t)1 << 31), "mikmeans: shard too large");
   hip_check(mk::launch_label_delta_rows(labels.data_ptr<int32_t>(), prev.data_ptr<int32_t>(),
                                         rows.data_ptr<int64_t>(), rcount.data_ptr<int64_t>(), rows.numel(),
@@ -618,9 +634,7 @@ void label_delta(const Tensor& labels, const Tensor& prev, const Tensor& list, c
   check_i32(labels, "labels", N);
   check_i32(prev, "prev", N);
   check_i32(count, "count", 1);
-  check_cuda(list, "list");
-  TORCH_CHECK(list.scalar_type() == at::kInt && list.dim() == 2 && list.size(1) == 2 && list.is_contiguous(),
-              "mikmeans: list must be contiguous int32 [cap, 2]");
+  check_delta_list(list);
   TORCH_CHECK(N < ((int64_t)1 << 31) && list.size(0) < ((int64_t)1 << 31), "mikmeans: shard too large");
   hip_check(mk::launch_label_delta(labels.data_ptr<int32_t>(), prev.data_ptr<int32_t>(), N,
                                    (int2*)list.data_ptr<int32_t>(), (int)list.size(0),
@@ -633,64 +647,48 @@ void update_delta(const Tensor& X, const Tensor& labels, int64_t K, const Tensor
                   const Tensor& cnt_slab, int64_t n_chunks, const c10::optional<Tensor>& weights,
                   const Tensor& col_exp, int64_t cnt_exp, const Tensor& list, const Tensor& count) {
   const int dt = dtype_of(X);
-  const int64_t ldx = check_points(X, dt);
-  const int64_t N = X.size(0);
-  const int D = (int)X.size(1);
-  check_i32(labels, "labels", N);
   check_i32(count, "count", 1);
-  check_cuda(list, "list");
-  TORCH_CHECK(list.scalar_type() == at::kInt && list.dim() == 2 && list.size(1) == 2 && list.is_contiguous(),
-              "mikmeans: list must be contiguous int32 [cap, 2]");
-  const int sw = mk::update_slice_width(dt, (int)K, D, true);
-  TORCH_CHECK(sw > 0, "mikmeans: incremental M-step needs an LDS slice (K too large)");
-  TORCH_CHECK(n_chunks % 8 == 0, "mikmeans: bad n_chunks");
-  check_i64(slab, "slab", n_chunks * K * D);
-  check_i64(cnt_slab, "cnt_slab", n_chunks * K);
-  if (weights.has_value()) check_f32(*weights, "weights", N);
-  check_i32(col_exp, "col_exp", D);
-  mk::UpdateArgs a;
-  a.X = X.data_ptr(); a.N = N; a.D = D; a.ldx = ldx;
-  a.labels = labels.data_ptr<int32_t>(); a.K = (int)K; a.n_chunks = (int)n_chunks;
-  a.slab = (long long*)slab.data_ptr<int64_t>(); a.cnt_slab = (long long*)cnt_slab.data_ptr<int64_t>();
-  a.weights = opt_ptr<const float>(weights);
-  a.col_exp = col_exp.data_ptr<int32_t>(); a.cnt_exp = (int)cnt_exp; a.clamp = 0;
+  check_delta_list(list);
+  int sw;
+  mk::UpdateArgs a = update_args(X, dt, -1, true, sw, labels, K, slab, cnt_slab, n_chunks, weights, col_exp, cnt_exp);
   a.dlist = (const int2*)list.data_ptr<int32_t>(); a.dcount = count.data_ptr<int32_t>();
   a.dcap = (int)list.size(0);
   hip_check(mk::launch_update(dt, a, stream()), "update_delta");
+}
+
+// The slab reduction behind reduce and reduce_delta (tot and count: the incremental one's)
+void reduce_into(const char* what, const Tensor& slab, const Tensor& cnt_slab, int64_t n_chunks, int64_t K,
+                 int64_t D, const c10::optional<Tensor>& slots, const Tensor& packed, const Tensor& col_exp,
+                 int64_t cnt_exp, const Tensor* tot = nullptr, const Tensor* count = nullptr, int64_t cap = 0) {
+  check_i64(slab, "slab", n_chunks * K * D);
+  check_i64(cnt_slab, "cnt_slab", n_chunks * K);
+  check_f64(packed, "packed", K * D + K + 2);
+  if (slots.has_value()) check_f64(*slots, "slots", mk::NSLOT * mk::SLOT_STRIDE);
+  check_i32(col_exp, "col_exp", D);
+  if (tot) {
+    check_i64(*tot, "tot", K * D + K);
+    check_i32(*count, "count", 1);
+  }
+  hip_check(mk::launch_reduce((const long long*)slab.data_ptr<int64_t>(),
+                              (const long long*)cnt_slab.data_ptr<int64_t>(), (int)n_chunks, (int)K,
+                              (int)D, col_exp.data_ptr<int32_t>(), (int)cnt_exp, opt_ptr<double>(slots),
+                              packed.data_ptr<double>(), stream(),
+                              tot ? (long long*)tot->data_ptr<int64_t>() : nullptr,
+                              tot ? count->data_ptr<int32_t>() : nullptr, (int)cap),
+            what);
 }
 
 // ... and the running totals it feeds (tot = [K*D sums | K counts] int64)
 void reduce_delta(const Tensor& slab, const Tensor& cnt_slab, int64_t n_chunks, int64_t K, int64_t D,
                   const c10::optional<Tensor>& slots, const Tensor& packed, const Tensor& col_exp,
                   int64_t cnt_exp, const Tensor& tot, const Tensor& count, int64_t cap) {
-  check_i64(slab, "slab", n_chunks * K * D);
-  check_i64(cnt_slab, "cnt_slab", n_chunks * K);
-  check_f64(packed, "packed", K * D + K + 2);
-  if (slots.has_value()) check_f64(*slots, "slots", mk::NSLOT * mk::SLOT_STRIDE);
-  check_i32(col_exp, "col_exp", D);
-  check_i64(tot, "tot", K * D + K);
-  check_i32(count, "count", 1);
-  hip_check(mk::launch_reduce((const long long*)slab.data_ptr<int64_t>(),
-                              (const long long*)cnt_slab.data_ptr<int64_t>(), (int)n_chunks, (int)K,
-                              (int)D, col_exp.data_ptr<int32_t>(), (int)cnt_exp, opt_ptr<double>(slots),
-                              packed.data_ptr<double>(), stream(), (long long*)tot.data_ptr<int64_t>(),
-                              count.data_ptr<int32_t>(), (int)cap),
-            "reduce_delta");
+  reduce_into("reduce_delta", slab, cnt_slab, n_chunks, K, D, slots, packed, col_exp, cnt_exp, &tot, &count, cap);
 }
 
 void reduce(const Tensor& slab, const Tensor& cnt_slab, int64_t n_chunks, int64_t K, int64_t D,
             const c10::optional<Tensor>& slots, const Tensor& packed, const Tensor& col_exp,
             int64_t cnt_exp) {
-  check_i64(slab, "slab", n_chunks * K * D);
-  check_i64(cnt_slab, "cnt_slab", n_chunks * K);
-  check_f64(packed, "packed", K * D + K + 2);
-  if (slots.has_value()) check_f64(*slots, "slots", mk::NSLOT * mk::SLOT_STRIDE);
-  check_i32(col_exp, "col_exp", D);
-  hip_check(mk::launch_reduce((const long long*)slab.data_ptr<int64_t>(),
-                              (const long long*)cnt_slab.data_ptr<int64_t>(), (int)n_chunks, (int)K,
-                              (int)D, col_exp.data_ptr<int32_t>(), (int)cnt_exp, opt_ptr<double>(slots),
-                              packed.data_ptr<double>(), stream()),
-            "reduce");
+  reduce_into("reduce", slab, cnt_slab, n_chunks, K, D, slots, packed, col_exp, cnt_exp);
 }
 
 // Wide-range column lo sums: out[k*nw + j] = 2^-exps[j] * sum_c slab[c][k][cols[j]].

@@ -56,4 +56,14 @@ inline int for_width(int dtype, int dpad, F&& f) {
   return detail::for_width_in<float>(dpad, f, seq);
 }
 
+// The same for one run-time value out of an explicit list: f(std::integral_constant<int, V>{})
+// for the V that equals v, and its result; hipErrorInvalidValue (1), without calling f, for a
+// value not in the list -- the list is what gets built.
+template <int... V, typename F>
+inline int for_value(int v, F&& f) {
+  int r = 1;
+  (void)((v == V && ((r = (int)f(std::integral_constant<int, V>{})), true)) || ...);
+  return r;
+}
+
 }  // namespace mk

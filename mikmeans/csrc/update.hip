@@ -9,14 +9,10 @@
 //    pattern; integer LDS adds are ~20x faster and are bound by moving their
 //    address + data dwords from VGPRs to the LDS (2 cycles per dword).
 // So every workgroup privatises a [K][SW] slice of the sums in LDS as FIXED-POINT
-// integers, TWO columns per 64-bit cell: a contribution q = rne(x * w * 2^e_col)
-// (|q| <= 2^20, per-column exponent e_col from the global column max) is formed
-// by ONE fma against the magic constant 1.5*2^23, whose result's bit pattern is
-// 0x4B400000 + q; the bit patterns of two adjacent columns are added as one
-// ds_add_u64 (3 dwords for 2 elements).  Modulo 2^64 the cell then holds
-//   sum(q_a) + sum(q_b) * 2^32 + n * 0x4B400000 * (1 + 2^32)
-// where n is the number of adds since the last flush (counted per label), and as
-// long as |sum(q)| < 2^31 for both columns the two sums decode exactly.  Each
+// integers, TWO columns per 64-bit cell (csrc/fx.h: the encode, the decode and the
+// no-wrap bound FX_LIM): a contribution q = rne(x * w * 2^e_col) (|q| <= 2^20,
+// per-column exponent e_col from the global column max) takes one fma, and the
+// pair of two adjacent columns one ds_add_u64 (3 dwords for 2 elements).  Each
 // label's add count is tracked; before any can reach 2^11 the workgroup flushes
 // its slice (decode, add into its int64 slab rows, zero) and carries on.
 // Integer addition is exact and associative: the M-step is bitwise identical for
@@ -37,6 +33,8 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
+#include "fx.h"
 #include "kernels.h"
 #include "plan.h"
 
@@ -44,10 +42,6 @@ namespace mk {
 
 constexpr int UPD_NT = 512;                 // one LDS-filling workgroup per CU
 using plan::UPD_LDS_MAX;
-using plan::FX_BITS;                        // |q| <= 2^20 per contribution
-constexpr int FX_LIM = (1 << (30 - FX_BITS)) * 2 - 1;  // adds per flush: 2047 * 2^20 < 2^31
-constexpr float FX_MAGIC = 12582912.0f;     // 1.5 * 2^23, bits 0x4B400000
-constexpr unsigned long long FX_MM = 0x4B4000004B400000ull;
 constexpr int UPD_MAX_PERIOD = 1024;        // rows between flush checks
 constexpr int UPD_NBUF = 3;                 // period buffers in the prefetch ring
 
@@ -72,20 +66,33 @@ __device__ __forceinline__ void unpack_any(const typename LoadT<BYTES>::type& w,
   }
 }
 
-// bits of (1.5*2^23 + rne(v * sc)); exact while |v * sc| <= 2^22.  CLAMP saturates
-// out-of-range contributions at +-2^20 (streams whose scale came from an earlier
-// batch), the bound FX_LIM's no-wrap guarantee assumes; the caller tracks the raw
-// range (rlo, rhi) so a batch that clamped is reported instead of kept silently.
-constexpr float FX_QMAX = 1048576.f;  // 2^FX_BITS
-template <bool CLAMP>
-__device__ __forceinline__ float fx_raw(float v, float sc) { return __builtin_fmaf(v, sc, FX_MAGIC); }
+// bits of fx_raw's 1.5*2^23 + rne(v * sc).  CLAMP saturates out-of-range contributions
+// at +-2^20 (streams whose scale came from an earlier batch), the bound FX_LIM's no-wrap
+// guarantee assumes.
 template <bool CLAMP>
 __device__ __forceinline__ uint32_t fx_clamp(float r) {
   if constexpr (CLAMP) r = __builtin_amdgcn_fmed3f(r, FX_MAGIC - FX_QMAX, FX_MAGIC + FX_QMAX);
   return __float_as_uint(r);
 }
+// The pair of two adjacent columns' contributions.  CLAMP tracks the raw range seen in
+// (rlo, rhi), so a batch that clamped is reported (fx_clamp_report) instead of kept silently.
 template <bool CLAMP>
-__device__ __forceinline__ uint32_t fx_bits(float v, float sc) { return fx_clamp<CLAMP>(fx_raw<CLAMP>(v, sc)); }
+__device__ __forceinline__ unsigned long long fx_contrib(float v0, float s0, float v1, float s1, float& rlo,
+                                                         float& rhi) {
+  const float r0 = fx_raw(v0, s0), r1 = fx_raw(v1, s1);
+  if constexpr (CLAMP) {
+    rlo = fminf(fminf(rlo, r0), r1);
+    rhi = fmaxf(fmaxf(rhi, r0), r1);
+  }
+  return fx_pair(fx_clamp<CLAMP>(r0), fx_clamp<CLAMP>(r1));
+}
+// One count per wave that saw a raw contribution outside +-2^20 (called by every lane)
+__device__ __forceinline__ void fx_clamp_report(int* clamp_count, float rlo, float rhi) {
+  if (clamp_count) {
+    const unsigned long long any = __ballot(!(rlo >= FX_MAGIC - FX_QMAX && rhi <= FX_MAGIC + FX_QMAX));
+    if (any && (threadIdx.x & 63) == __builtin_ctzll(any)) atomicAdd(clamp_count, 1);
+  }
+}
 // Residual pass (wide-range columns): bits of 1.5*2^23 + rne((v*sc - rne(v*sc)) * sc2).
 // v*sc - rne(v*sc) is exact in f32 (|.| <= 1/2), so the hi pass (col_exp) plus this lo
 // pass (col_exp + 20) quantise x to 2^-41 of its column maximum instead of 2^-21.
@@ -96,7 +103,7 @@ __device__ __forceinline__ uint32_t fx_bits_resid(float v, float sc, float sc2) 
 }
 
 __device__ __forceinline__ long long fx_q(float v, float sc) {
-  return (long long)(int)(fx_bits<true>(v, sc) - 0x4B400000u);
+  return (long long)(int)(fx_clamp<true>(fx_raw(v, sc)) - 0x4B400000u);
 }
 
 // LDS: cells [K+1][LDc] u64 (row K is a sink for rows outside the chunk, so the hot
@@ -132,10 +139,6 @@ struct UpdLayout {
   __device__ int pos(int k, int p) const { return at(k, p / npl, p % npl); }
 };
 
-// nadd[k]: adds since label k's last flush in bits 0..30; bit 31 = "k's slab row
-// already holds a partial sum" (then a flush adds instead of storing).
-constexpr unsigned NADD_MASK = 0x7fffffffu, NADD_WRITTEN = 0x80000000u;
-
 // Mid-chunk flush of every label whose add count reached `thresh`: list them, then
 // decode their cells with one (label, pair) per thread so the slab read-modify-writes
 // of a label are contiguous across lanes.  Called by all threads after an LDS barrier.
@@ -162,15 +165,10 @@ __device__ void upd_flush_hot(const UpdateArgs& a, const UpdLayout& L, char* m, 
     const int k = hot[e / NP], p = e % NP;
     const unsigned na = nadd[k];
     const int q = k * L.LDc + L.pos(k, p);
-    const unsigned long long T = cells[q] - (unsigned long long)(na & NADD_MASK) * FX_MM;
+    const FxSums t = fx_decode(cells[q], na);
     cells[q] = 0;
-    const int lo = (int)(uint32_t)T;
-    const long long hi = (long long)(T - (unsigned long long)(long long)lo) >> 32;
-    if (2 * p < cols) {
-      long long* dst = a.slab + (int64_t)chunk * a.K * a.D + (int64_t)k * a.D + slice * SW + 2 * p;
-      if (na & NADD_WRITTEN) { dst[0] += lo; dst[1] += hi; }
-      else { dst[0] = lo; dst[1] = hi; }
-    }
+    if (2 * p < cols)
+      fx_put(a.slab + (int64_t)chunk * a.K * a.D + (int64_t)k * a.D + slice * SW + 2 * p, t, na);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < nh; i += blockDim.x) {
@@ -178,8 +176,7 @@ __device__ void upd_flush_hot(const UpdateArgs& a, const UpdLayout& L, char* m, 
     const unsigned na = nadd[k];
     if (slice == 0) {
       const long long c = W ? L.wcnt(m)[k] : (long long)(na & NADD_MASK);
-      long long* cd = a.cnt_slab + (int64_t)chunk * a.K + k;
-      if (na & NADD_WRITTEN) *cd += c; else *cd = c;
+      fx_put(a.cnt_slab + (int64_t)chunk * a.K + k, c, na);
     }
     if (W) L.wcnt(m)[k] = 0;
     nadd[k] = NADD_WRITTEN;
@@ -200,21 +197,14 @@ __device__ void upd_flush_all(const UpdateArgs& a, const UpdLayout& L, char* m, 
   for (int e = threadIdx.x; e < a.K * NP; e += blockDim.x) {
     const int k = e / NP, p = e % NP;
     const unsigned na = nadd[k];
-    const unsigned long long T = cells[k * L.LDc + L.pos(k, p)] - (unsigned long long)(na & NADD_MASK) * FX_MM;
-    const int lo = (int)(uint32_t)T;
-    const long long hi = (long long)(T - (unsigned long long)(long long)lo) >> 32;
-    if (2 * p < cols) {
-      long long* dst = slab + (int64_t)k * a.D + 2 * p;
-      if (na & NADD_WRITTEN) { dst[0] += lo; dst[1] += hi; }
-      else { dst[0] = lo; dst[1] = hi; }
-    }
+    const FxSums t = fx_decode(cells[k * L.LDc + L.pos(k, p)], na);
+    if (2 * p < cols) fx_put(slab + (int64_t)k * a.D + 2 * p, t, na);
   }
   if (slice == 0) {
     for (int k = threadIdx.x; k < a.K; k += blockDim.x) {
       const unsigned na = nadd[k];
       const long long c = upd_wcounts(a) ? L.wcnt(m)[k] : (long long)(na & NADD_MASK);
-      long long* dst = a.cnt_slab + (int64_t)chunk * a.K + k;
-      if (na & NADD_WRITTEN) *dst += c; else *dst = c;
+      fx_put(a.cnt_slab + (int64_t)chunk * a.K + k, c, na);
     }
   }
 }
@@ -445,16 +435,9 @@ __global__ __launch_bounds__(NT) void update_kernel(UpdateArgs a, int n_slices,
         const float s0 = W ? sc[e] * wt_[u] : sc[e];
         const float s1 = W ? sc[e + 1] * wt_[u] : sc[e + 1];
         if constexpr (RESID)
-          v[e / 2] = (unsigned long long)fx_bits_resid(f[e], s0, sc2[e]) |
-                     ((unsigned long long)fx_bits_resid(f[e + 1], s1, sc2[e + 1]) << 32);
-        else {
-          const float r0 = fx_raw<CLAMP>(f[e], s0), r1 = fx_raw<CLAMP>(f[e + 1], s1);
-          if constexpr (CLAMP) {
-            rlo = fminf(fminf(rlo, r0), r1);
-            rhi = fmaxf(fmaxf(rhi, r0), r1);
-          }
-          v[e / 2] = (unsigned long long)fx_clamp<CLAMP>(r0) | ((unsigned long long)fx_clamp<CLAMP>(r1) << 32);
-        }
+          v[e / 2] = fx_pair(fx_bits_resid(f[e], s0, sc2[e]), fx_bits_resid(f[e + 1], s1, sc2[e + 1]));
+        else
+          v[e / 2] = fx_contrib<CLAMP>(f[e], s0, f[e + 1], s1, rlo, rhi);
       }
       if constexpr (W)
         if (wcounter)  // weighted counts: one add per row (slice 0 only)
@@ -548,12 +531,7 @@ __global__ __launch_bounds__(NT) void update_kernel(UpdateArgs a, int n_slices,
     }
   }
   upd_flush_all<SW>(a, L, smem, slice, chunk);
-  if constexpr (CLAMP) {
-    if (a.clamp_count) {
-      const unsigned long long any = __ballot(!(rlo >= FX_MAGIC - FX_QMAX && rhi <= FX_MAGIC + FX_QMAX));
-      if (any && (threadIdx.x & 63) == __builtin_ctzll(any)) atomicAdd(a.clamp_count, 1);
-    }
-  }
+  if constexpr (CLAMP) fx_clamp_report(a.clamp_count, rlo, rhi);
 }
 
 // ---------------------------------------------------------------------------
@@ -585,22 +563,16 @@ __device__ void ks_flush(const UpdateArgs& a, char* m, int kq, int kn, int ldc, 
     const unsigned na = nadd[kl];
     if ((na & NADD_MASK) < thresh) continue;
     const int q = kl * ldc + (p % NPL) * LPR + p / NPL;
-    const unsigned long long T_ = cells[q] - (unsigned long long)(na & NADD_MASK) * FX_MM;
+    const FxSums t = fx_decode(cells[q], na);
     cells[q] = 0;
-    const int lo = (int)(uint32_t)T_;
-    const long long hi = (long long)(T_ - (unsigned long long)(long long)lo) >> 32;
-    if (2 * p < a.D) {
-      long long* dst = a.slab + (int64_t)chunk * a.K * a.D + (int64_t)(k0 + kl) * a.D + 2 * p;
-      if (na & NADD_WRITTEN) { dst[0] += lo; if (2 * p + 1 < a.D) dst[1] += hi; }
-      else { dst[0] = lo; if (2 * p + 1 < a.D) dst[1] = hi; }
-    }
+    if (2 * p < a.D)
+      fx_put(a.slab + (int64_t)chunk * a.K * a.D + (int64_t)(k0 + kl) * a.D + 2 * p, t, na, 2 * p + 1 < a.D);
   }
   __syncthreads();
   for (int kl = threadIdx.x; kl < kn; kl += blockDim.x) {
     const unsigned na = nadd[kl];
     if ((na & NADD_MASK) < thresh) continue;
-    long long* cd = a.cnt_slab + (int64_t)chunk * a.K + k0 + kl;
-    if (na & NADD_WRITTEN) *cd += (long long)(na & NADD_MASK); else *cd = (long long)(na & NADD_MASK);
+    fx_put(a.cnt_slab + (int64_t)chunk * a.K + k0 + kl, (long long)(na & NADD_MASK), na);
     nadd[kl] = NADD_WRITTEN;
   }
   __syncthreads();
@@ -696,13 +668,7 @@ __global__ __launch_bounds__(plan::KS_NT) void update_ks_kernel(UpdateArgs a, in
     unsigned long long* dst = cells + kl * ldc + cc;
 #pragma unroll
     for (int e = 0; e < V; e += 2) {
-      const float r0 = fx_raw<CLAMP>(f[e], sc[e]), r1 = fx_raw<CLAMP>(f[e + 1], sc[e + 1]);
-      if constexpr (CLAMP) {
-        rlo = fminf(fminf(rlo, r0), r1);
-        rhi = fmaxf(fmaxf(rhi, r0), r1);
-      }
-      const unsigned long long v = (unsigned long long)fx_clamp<CLAMP>(r0) |
-                                   ((unsigned long long)fx_clamp<CLAMP>(r1) << 32);
+      const unsigned long long v = fx_contrib<CLAMP>(f[e], sc[e], f[e + 1], sc[e + 1], rlo, rhi);
       __hip_atomic_fetch_add(dst + (e / 2) * LPR, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
     if (cc == 0) {
@@ -765,12 +731,7 @@ __global__ __launch_bounds__(plan::KS_NT) void update_ks_kernel(UpdateArgs a, in
   }
   __syncthreads();
   ks_flush<T, LPR>(a, smem, kq, kn, ldc, NPAIR, k0, chunk, 0u);
-  if constexpr (CLAMP) {
-    if (a.clamp_count) {
-      const unsigned long long any = __ballot(!(rlo >= FX_MAGIC - FX_QMAX && rhi <= FX_MAGIC + FX_QMAX));
-      if (any && lane == __builtin_ctzll(any)) atomicAdd(a.clamp_count, 1);
-    }
-  }
+  if constexpr (CLAMP) fx_clamp_report(a.clamp_count, rlo, rhi);
 }
 
 // Fallback for K too large to privatise even 2 columns: direct int64 global atomics
@@ -810,8 +771,6 @@ int update_slice_width(int dtype, int K, int D, bool weighted) {
   return choose_sw(dtype, K, D, weighted, &ldc);
 }
 
-static int esize(int dtype);
-
 // The K-split kernel serves plain full passes where the slice kernel needs 2+ slices of
 // under 128 B per row: N=1e8 D=128 K=1024 bf16 (64-B pieces) 5.20 -> 4.67 ms, N=1e7 D=64
 // K=4096 (16-B pieces) 0.62 -> 0.44 ms; with 128-B or wider pieces (cfg5's 64 bf16
@@ -836,16 +795,20 @@ int update_n_chunks(int dtype, int K, int D, int64_t N, bool weighted) {
 
 int fixed_exp(double maxabs) { return plan::fixed_exp(maxabs); }
 
+// Opt Kernel in to UPD_LDS_MAX of dynamic LDS (past the 64 KiB default), once per process
+// (fold.h fold_lds_optin's sibling for both M-step kernels).
+template <auto Kernel>
+static void upd_lds_optin() {
+  static const hipError_t once =
+      hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)UPD_LDS_MAX);
+  (void)once;
+}
+
 template <typename T, int SW, int MODE, int NT, int NBF = UPD_NBUF, int PER = UPD_MAX_PERIOD>
 static hipError_t launch_nt(const UpdateArgs& a, int ldc, hipStream_t s) {
   const int n_slices = (a.D + SW - 1) / SW;
   const int64_t rows_per_chunk = (a.N + a.n_chunks - 1) / a.n_chunks;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)update_kernel<T, SW, MODE, NT, NBF, PER>,
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)UPD_LDS_MAX);
-    attr = true;
-  }
+  upd_lds_optin<update_kernel<T, SW, MODE, NT, NBF, PER>>();
   size_t lds = upd_lds_bytes(a.K, ldc, (MODE & (UPD_WEIGHTED | UPD_DELTA)) != 0);
   if constexpr ((MODE & UPD_GSTAGE) != 0) lds += (size_t)NBF * upd_period<T, SW, NT, PER>() * 8;
   hipLaunchKernelGGL((update_kernel<T, SW, MODE, NT, NBF, PER>), dim3(a.n_chunks * n_slices), dim3(NT), lds, s, a,
@@ -892,71 +855,38 @@ static hipError_t launch_sw(const UpdateArgs& a, int ldc, hipStream_t s) {
   else return launch_nt<T, SW, MODE, NT>(a, ldc, s);
 }
 
+// The one place that decides which update_kernel modes are built: the run-time MODE word of a
+// pass, dispatched over the list of the 20 modes per (T, SW).
 template <typename T, int SW>
 static hipError_t launch_clamp(const UpdateArgs& a, int ldc, hipStream_t s) {
-  const int mode = (a.clamp ? UPD_CLAMP : 0) | (a.weights ? UPD_WEIGHTED : 0) |
-                   (ldc == SW / 2 ? UPD_SWZ : 0);
-  if (a.col_exp2) {  // residual (lo) pass of the wide-range columns: never clamped / incremental
-    if (a.clamp || a.dlist || a.rows) return hipErrorInvalidValue;
-    switch (mode) {
-      case 0: return launch_sw<T, SW, UPD_RESID>(a, ldc, s);
-      case 2: return launch_sw<T, SW, UPD_RESID | UPD_WEIGHTED>(a, ldc, s);
-      case 4: return launch_sw<T, SW, UPD_RESID | UPD_SWZ>(a, ldc, s);
-      default: return launch_sw<T, SW, UPD_RESID | UPD_WEIGHTED | UPD_SWZ>(a, ldc, s);
-    }
-  }
-  if (a.rows) {  // gathered mini-batch rows: plain (bounded, unclamped) passes only
-    if (a.clamp || a.dlist) return hipErrorInvalidValue;
-    switch (mode) {
-      case 0: return launch_sw<T, SW, UPD_GATHER | UPD_GSTAGE>(a, ldc, s);
-      case 2: return launch_sw<T, SW, UPD_GATHER | UPD_WEIGHTED>(a, ldc, s);
-      case 4: return launch_sw<T, SW, UPD_GATHER | UPD_SWZ | UPD_GSTAGE>(a, ldc, s);
-      default: return launch_sw<T, SW, UPD_GATHER | UPD_WEIGHTED | UPD_SWZ>(a, ldc, s);
-    }
-  }
-  if (a.dlist) {  // incremental M-step (Lloyd: never clamped; weights read at run time)
-    if (a.clamp) return hipErrorInvalidValue;
-    return (mode & UPD_SWZ) ? launch_sw<T, SW, UPD_DELTA | UPD_SWZ>(a, ldc, s)
-                            : launch_sw<T, SW, UPD_DELTA>(a, ldc, s);
-  }
-  switch (mode) {
-    case 0: return launch_sw<T, SW, 0>(a, ldc, s);
-    case 1: return launch_sw<T, SW, 1>(a, ldc, s);
-    case 2: return launch_sw<T, SW, 2>(a, ldc, s);
-    case 3: return launch_sw<T, SW, 3>(a, ldc, s);
-    case 4: return launch_sw<T, SW, 4>(a, ldc, s);
-    case 5: return launch_sw<T, SW, 5>(a, ldc, s);
-    case 6: return launch_sw<T, SW, 6>(a, ldc, s);
-    default: return launch_sw<T, SW, 7>(a, ldc, s);
-  }
+  // residual (lo) pass of the wide-range columns and gathered mini-batch rows: plain (bounded,
+  // unclamped) passes only; incremental M-step (Lloyd): never clamped
+  if ((a.col_exp2 || a.rows) && (a.clamp || a.dlist)) return hipErrorInvalidValue;
+  if ((a.col_exp2 && a.rows) || (a.dlist && a.clamp)) return hipErrorInvalidValue;
+  const bool w = a.weights && !a.dlist;   // (incremental: weights read at run time)
+  const int mode = (a.clamp ? UPD_CLAMP : 0) | (w ? UPD_WEIGHTED : 0) | (ldc == SW / 2 ? UPD_SWZ : 0) |
+                   (a.col_exp2 ? UPD_RESID : 0) | (a.dlist ? UPD_DELTA : 0) |
+                   (a.rows ? UPD_GATHER | (w ? 0 : UPD_GSTAGE) : 0);   // indices staged only when unweighted
+  constexpr int C = UPD_CLAMP, W = UPD_WEIGHTED, Z = UPD_SWZ, R = UPD_RESID, D = UPD_DELTA, G = UPD_GATHER,
+                GS = UPD_GATHER | UPD_GSTAGE;   // (G, G | Z: what launch_sw falls back to from GS)
+  return (hipError_t)for_value<0, C, W, C | W, Z, C | Z, W | Z, C | W | Z, R, R | W, R | Z, R | W | Z, GS, G | W,
+                               GS | Z, G | W | Z, G, G | Z, D, D | Z>(
+      mode, [&](auto m) { return launch_sw<T, SW, decltype(m)::value>(a, ldc, s); });
 }
 
 template <typename T>
 static hipError_t launch_update_t(const UpdateArgs& a, hipStream_t s, int sw, int ldc) {
-  switch (sw) {
-    case 64: return launch_clamp<T, 64>(a, ldc, s);
-    case 32: return launch_clamp<T, 32>(a, ldc, s);
-    case 16: return launch_clamp<T, 16>(a, ldc, s);
-    case 8: return launch_clamp<T, 8>(a, ldc, s);
-    case 4: return launch_clamp<T, 4>(a, ldc, s);
-    case 2: return launch_clamp<T, 2>(a, ldc, s);
-    case 0:
-      // caller zeroed slab[K*D] + cnt_slab[K] (n_chunks == 1)
-      hipLaunchKernelGGL((update_global_kernel<T>), dim3((unsigned)((a.N + 3) / 4)), dim3(256), 0,
-                         s, a);
-      return hipGetLastError();
+  if (sw == 0) {   // caller zeroed slab[K*D] + cnt_slab[K] (n_chunks == 1)
+    hipLaunchKernelGGL((update_global_kernel<T>), dim3((unsigned)((a.N + 3) / 4)), dim3(256), 0, s, a);
+    return hipGetLastError();
   }
-  return hipErrorInvalidValue;
+  return (hipError_t)for_value<64, 32, 16, 8, 4, 2>(
+      sw, [&](auto w) { return launch_clamp<T, decltype(w)::value>(a, ldc, s); });
 }
 
 template <typename T, int LPR, int GM, bool CLAMP, bool GATHER = false>
 static hipError_t launch_ks_t(const UpdateArgs& a, const plan::KsPlan& kp, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)update_ks_kernel<T, LPR, GM, CLAMP, GATHER>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)UPD_LDS_MAX);
-    attr = true;
-  }
+  upd_lds_optin<update_ks_kernel<T, LPR, GM, CLAMP, GATHER>>();
   const int64_t rows_per_chunk = (a.N + a.n_chunks - 1) / a.n_chunks;
   const size_t lds = plan::ks_lds_bytes(kp.kq, kp.ldc) + (GATHER ? plan::KS_GLIST_BYTES : 0);
   if (lds > UPD_LDS_MAX) return hipErrorInvalidValue;
@@ -965,28 +895,18 @@ static hipError_t launch_ks_t(const UpdateArgs& a, const plan::KsPlan& kp, hipSt
   return hipGetLastError();
 }
 
-template <typename T, int LPR>
-static hipError_t launch_ks_l(const UpdateArgs& a, const plan::KsPlan& kp, hipStream_t s) {
-  if (a.rows) {  // gathered mini-batch rows (bounded scales: never clamped)
-    if (a.clamp) return hipErrorInvalidValue;
-    if (kp.gm == 6) return launch_ks_t<T, LPR, 6, false, true>(a, kp, s);
-    if (kp.gm == 3) return launch_ks_t<T, LPR, 3, false, true>(a, kp, s);
-    return launch_ks_t<T, LPR, 2, false, true>(a, kp, s);
-  }
-  if (kp.gm == 6) return a.clamp ? launch_ks_t<T, LPR, 6, true>(a, kp, s) : launch_ks_t<T, LPR, 6, false>(a, kp, s);
-  if (kp.gm == 3) return a.clamp ? launch_ks_t<T, LPR, 3, true>(a, kp, s) : launch_ks_t<T, LPR, 3, false>(a, kp, s);
-  return a.clamp ? launch_ks_t<T, LPR, 2, true>(a, kp, s) : launch_ks_t<T, LPR, 2, false>(a, kp, s);
-}
-
+// LPR x GM (2, 3 or 6 row groups in flight; 2 for any other plan) x {plain, clamped, gathered}
 template <typename T>
 static hipError_t launch_ks(const UpdateArgs& a, const plan::KsPlan& kp, hipStream_t s) {
-  switch (kp.lpr) {
-    case 8: return launch_ks_l<T, 8>(a, kp, s);
-    case 16: return launch_ks_l<T, 16>(a, kp, s);
-    case 32: return launch_ks_l<T, 32>(a, kp, s);
-    case 64: return launch_ks_l<T, 64>(a, kp, s);
-  }
-  return hipErrorInvalidValue;
+  if (a.rows && a.clamp) return hipErrorInvalidValue;   // gathered mini-batch rows (bounded scales: never clamped)
+  return (hipError_t)for_value<8, 16, 32, 64>(kp.lpr, [&](auto l) {
+    return for_value<2, 3, 6>(kp.gm == 6 || kp.gm == 3 ? kp.gm : 2, [&](auto g) {
+      return for_value<0, 1, 2>(a.rows ? 2 : a.clamp ? 1 : 0, [&](auto v) {
+        constexpr int V = decltype(v)::value;
+        return launch_ks_t<T, decltype(l)::value, decltype(g)::value, V == 1, V == 2>(a, kp, s);
+      });
+    });
+  });
 }
 
 hipError_t launch_update(int dtype, const UpdateArgs& a, hipStream_t s) {
@@ -1130,6 +1050,31 @@ hipError_t launch_reduce_cols(const long long* slab, int n_chunks, int K, int D,
 // integers, so the result is.
 constexpr int LD_R = 16;
 
+// The tail both list kernels share.  A thread holds R rows (row(t) their ids, lab / old their new
+// and previous labels) of which those in the mask m changed: the workgroup's count in wg_n
+// (zeroed before a barrier by the caller), one global reservation per workgroup, then
+// prev[i] = lab and the (i, old) entries below cap.
+template <int R, typename Row>
+__device__ __forceinline__ void label_delta_append(unsigned m, Row&& row, const int* lab, const int* old,
+                                                   int32_t* __restrict__ prev, int2* __restrict__ list, int cap,
+                                                   int* count, int& wg_n, int& wg_base) {
+  const int n = __popc(m);
+  const int off = n ? atomicAdd(&wg_n, n) : 0;
+  __syncthreads();
+  if (threadIdx.x == 0) wg_base = wg_n ? atomicAdd(count, wg_n) : 0;
+  __syncthreads();
+  int pos = wg_base + off;
+#pragma unroll
+  for (int t = 0; t < R; ++t) {
+    if (m >> t & 1u) {
+      const int64_t i = row(t);
+      prev[i] = lab[t];
+      if (pos < cap) list[pos] = make_int2((int)i, old[t]);
+      ++pos;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void label_delta_kernel(const int32_t* __restrict__ labels,
                                                           int32_t* __restrict__ prev, int64_t N,
                                                           int2* __restrict__ list, int cap,
@@ -1149,21 +1094,7 @@ __global__ __launch_bounds__(256) void label_delta_kernel(const int32_t* __restr
       if (lab[t] != old[t]) m |= 1u << t;
     }
   }
-  const int n = __popc(m);
-  const int off = n ? atomicAdd(&wg_n, n) : 0;
-  __syncthreads();
-  if (threadIdx.x == 0) wg_base = wg_n ? atomicAdd(count, wg_n) : 0;
-  __syncthreads();
-  int pos = wg_base + off;
-#pragma unroll
-  for (int t = 0; t < LD_R; ++t) {
-    if (m >> t & 1u) {
-      const int64_t i = b0 + t * 256;
-      prev[i] = lab[t];
-      if (pos < cap) list[pos] = make_int2((int)i, old[t]);
-      ++pos;
-    }
-  }
+  label_delta_append<LD_R>(m, [&](int t) { return b0 + t * 256; }, lab, old, prev, list, cap, count, wg_n, wg_base);
 }
 
 // The same over a candidate list rows[0..*rcount) (the bounded E-step re-assigned only those
@@ -1201,20 +1132,7 @@ __global__ __launch_bounds__(256) void label_delta_rows_kernel(const int32_t* __
 #pragma unroll
     for (int t = 0; t < LDR_R; ++t)
       if (i[t] >= 0 && lab[t] != old[t]) ch |= 1u << t;
-    const int n = __popc(ch);
-    const int off = n ? atomicAdd(&wg_n, n) : 0;
-    __syncthreads();
-    if (threadIdx.x == 0) wg_base = wg_n ? atomicAdd(count, wg_n) : 0;
-    __syncthreads();
-    int pos = wg_base + off;
-#pragma unroll
-    for (int t = 0; t < LDR_R; ++t) {
-      if (ch >> t & 1u) {
-        prev[i[t]] = lab[t];
-        if (pos < cap) list[pos] = make_int2((int)i[t], old[t]);
-        ++pos;
-      }
-    }
+    label_delta_append<LDR_R>(ch, [&](int t) { return i[t]; }, lab, old, prev, list, cap, count, wg_n, wg_base);
     __syncthreads();   // (wg_n / wg_base are rewritten by the next pass)
   }
 }

@@ -114,13 +114,39 @@ def cmd_run(a) -> int:
         t["m"].assign(eng.X, t["pack"], t["cn"], eng.xn, t["lab"], t["mind"], t["slots"], t["kpad"], dpad, True,
                       None)
 
-    def run_update(t):   # the full M-step pass on the engine's labels into each module's own slab
+    if a.what == "update":   # one set of inputs per --mode (the head's), the same for every module
+        from mikmeans import ops
+
+        g = torch.Generator(device=dev).manual_seed(1)
+        uw = torch.rand(a.n, generator=g, device=dev) + 0.5 if a.mode == "weighted" else None
+        ucol, ucnt = ops.fixed_exps(eng.X, uw) if uw is not None else (eng.col_exp, eng.cnt_exp)
+        ukw = {}
+        if a.mode == "resid":      # the lo pass of two columns
+            ukw["col_exp2"] = torch.full_like(ucol, -1000)
+            ukw["col_exp2"][[0, eng.Dp // 2]] = ucol[[0, eng.Dp // 2]] + 20
+        if a.mode == "gather":     # a permutation with repeats
+            ukw["rows"] = torch.randperm(a.n, generator=g, device=dev)
+            ukw["rows"][1::5] = ukw["rows"][0::5][: ukw["rows"][1::5].numel()]
+        if a.mode == "delta":      # every tenth row came from the next label
+            prev = eng.labels.clone()
+            prev[::10] = (prev[::10] + 1) % a.k
+            ulist = torch.empty((a.n // 10 + 8, 2), dtype=torch.int32, device=dev)
+            ucount = torch.zeros(1, dtype=torch.int32, device=dev)
+            mods["head"].label_delta(eng.labels, prev, ulist, ucount)
+
+    def run_update(t):   # one M-step pass on the engine's labels into each module's own slab
         m = t["m"]
         if "slab" not in t:
-            t["nch"] = m.update_n_chunks(code, a.k, eng.Dp, a.n, False)
-            t["slab"] = torch.empty(t["nch"] * a.k * eng.Dp, dtype=torch.int64, device=dev)
-            t["cnt"] = torch.empty(t["nch"] * a.k, dtype=torch.int64, device=dev)
-        m.update(eng.X, eng.labels, a.k, t["slab"], t["cnt"], t["nch"], None, eng.col_exp, eng.cnt_exp, False)
+            t["nch"] = m.update_n_chunks(code, a.k, eng.Dp, a.n, a.mode in ("weighted", "delta"))
+            # (zeros: the residual pass leaves the slices without a wide column unwritten)
+            t["slab"] = torch.zeros(t["nch"] * a.k * eng.Dp, dtype=torch.int64, device=dev)
+            t["cnt"] = torch.zeros(t["nch"] * a.k, dtype=torch.int64, device=dev)
+            t["cc"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        if a.mode == "delta":
+            m.update_delta(eng.X, eng.labels, a.k, t["slab"], t["cnt"], t["nch"], None, ucol, ucnt, ulist, ucount)
+        else:
+            m.update(eng.X, eng.labels, a.k, t["slab"], t["cnt"], t["nch"], uw, ucol, ucnt, a.mode == "clamp",
+                     clamp_count=t["cc"] if a.mode == "clamp" else None, **ukw)
 
     def run_blobs(t):    # the on-device generator (+ fused row norms) into each module's own buffer
         if "bx" not in t:
@@ -220,7 +246,8 @@ def cmd_run(a) -> int:
         red = {tag: (t["slab"].view(t["nch"], -1).sum(0), t["cnt"].view(t["nch"], -1).sum(0)) for tag, t in per.items()}
         for tag, t in per.items():
             t["same"] = bool(torch.equal(red[tag][0], red["head"][0]) and torch.equal(red[tag][1], red["head"][1]))
-    out = {"n": a.n, "d": a.d, "k": a.k, "dtype": a.dtype, "what": a.what, "variants": {}}
+    out = {"n": a.n, "d": a.d, "k": a.k, "dtype": a.dtype, "what": a.what,
+           **({"mode": a.mode} if a.what == "update" else {}), "variants": {}}
     for tag, t in per.items():
         med = statistics.median(t["ts"])
         # a round's own median, and their spread: the box's round-to-round noise
@@ -254,6 +281,8 @@ def main(argv=None) -> int:
     r.add_argument("--reps", type=int, default=5)
     r.add_argument("--what", default="assign", choices=["assign", "update", "blobs", "colstats", "rownorms",
                                                         "transform", "topk", "ivf_scan", "ivf_range"])
+    r.add_argument("--mode", default="plain", choices=["plain", "weighted", "clamp", "resid", "gather", "delta"],
+                   help="update: the pass (each reaches another build of the M-step kernels)")
     r.add_argument("--m", type=int, default=8,
                    help="topk / ivf_scan: list length; ivf_range: the radius is the m-th nearest row's distance")
     r.add_argument("--nq", type=int, default=10_000, help="ivf_scan / ivf_range: queries (the first rows)")

@@ -2,7 +2,8 @@
 // tests/test_native_host.py with -fsanitize=address,undefined).  For both element sizes,
 // for_width must reach a case -- with the matching type and width tags -- for exactly the
 // widths plan::assign_dpad returns over D = 1..1024, and refuse every other width in 1..2048;
-// prints "ok <cases>" or the first violation.
+// for_value must do the same for an explicit list of values.  Prints "ok <cases>" or the first
+// violation.
 #include <stdio.h>
 
 #include <set>
@@ -43,6 +44,21 @@ int main() {
     // a case's own result comes back unchanged
     if (mk::for_width(dtype, *widths.begin(), [](auto, auto) { return 7; }) != 7) return fail("result", es, 0, 0);
   }
+  // for_value: every value of a list reaches its case once, with its tag; every other value in
+  // a window around the list is refused without a call
+  const std::set<int> list = {0, 1, 2, 3, 8, 12, 32, 38, 64, 192, 196};
+  for (int v = -64; v <= 320; ++v) {
+    int calls = 0, got = -1000;
+    const int r = mk::for_value<0, 1, 2, 3, 8, 12, 32, 38, 64, 192, 196>(v, [&](auto t) {
+      ++calls;
+      got = decltype(t)::value;
+      return 0;
+    });
+    ++cases;
+    if (list.count(v) ? (r != 0 || calls != 1 || got != v) : (r != 1 || calls != 0))
+      return fail(list.count(v) ? "value not reached" : "value not refused", v, r, calls);
+  }
+  if (mk::for_value<5, 9>(9, [](auto) { return 7; }) != 7) return fail("value result", 9, 0, 0);
   printf("ok %lld\n", cases);
   return 0;
 }

@@ -352,3 +352,166 @@ def test_resident_and_streamed_fit_agree_at_the_wide_column_threshold(native):
     assert b.memory_plan_["mode"] == "streaming"
     assert torch.equal(a.cluster_centers_, b.cluster_centers_)
     assert torch.equal(a.labels_.cpu(), torch.as_tensor(b.labels_).cpu())
+
+
+# ---- the slab against an exact integer sum (csrc/fx.h, csrc/update.hip) -----------------------
+FX_LIM = 2047   # csrc/fx.h: adds a cell takes between two flushes
+_SLAB_SHAPES = {   # name: (dtype, D, K)
+    "bf16_d64": (torch.bfloat16, 64, 16),      # one 64-column slice, the 1024-thread build
+    "f32_d32": (torch.float32, 32, 8),
+    "bf16_d128": (torch.bfloat16, 128, 1024),  # the K-split kernel, or four 32-column slices
+    "f32_d8_global": (torch.float32, 8, 12_000),
+}
+_SLAB_CASES = ([("bf16_d64", m) for m in ("plain", "weighted", "clamp", "resid", "gather")] +
+               [("f32_d32", m) for m in ("plain", "weighted")] +
+               [("bf16_d128", m) for m in ("plain", "plain_slices", "gather", "gather_slices")])
+_SLAB_PARAMS = ([(s, m, lab) for s, m in _SLAB_CASES for lab in ("one_label", "mixed")] +
+                [("bf16_d64", "delta", "moved"), ("f32_d8_global", "plain", "mixed")])
+_slab_cache = {}
+
+
+def _slab_chunks(C, dt, K, D, weighted, per_chunk):
+    """(N, n_chunks) with N = n_chunks * per_chunk rows and n_chunks the launcher's for that N."""
+    nch = C.update_n_chunks(dt, K, D, 50_000, weighted)
+    for _ in range(4):
+        n = nch * per_chunk
+        if C.update_n_chunks(dt, K, D, n, weighted) == nch:
+            return n, nch
+        nch = C.update_n_chunks(dt, K, D, n, weighted)
+    raise AssertionError("no fixed point of update_n_chunks")
+
+
+def _slab_inputs(shape, labels, n):
+    """X [n, D], labels [n], weights [n] and a gather list [n] on the CPU, made once per key."""
+    key = (shape, labels, n)
+    if key not in _slab_cache:
+        dtype, d, k = _SLAB_SHAPES[shape]
+        g = torch.Generator().manual_seed(d + k + n)
+        X = (torch.randn(n, d, generator=g) * 2 + torch.arange(d) * 0.125).to(dtype)
+        if labels == "one_label":
+            lab = torch.full((n,), k - 1, dtype=torch.int32)
+        else:
+            lab = torch.randint(0, k, (n,), generator=g, dtype=torch.int32)
+            lab[::3] = -1
+        w = torch.rand(n, generator=g) + 0.5
+        rows = torch.randperm(n, generator=g)
+        rows[1::5] = rows[0::5][: rows[1::5].numel()]   # a permutation with repeats
+        _slab_cache[key] = (X, lab, w, rows)
+    return _slab_cache[key]
+
+
+def _slab_reference(X, lab, K, col_exp, w=None, cnt_exp=0, rows=None, col_exp2=None):
+    """Exact int64 sums [K, D] and counts [K] of q = round-half-even(f64(x) * f64(f32(2^e * w))) -- the
+    product is exact in float64, so this is the kernel's one fma against FX_MAGIC -- and, for the
+    residual pass, of the two-step rule of fx_bits_resid."""
+    n, d = lab.numel(), X.shape[1]
+    sums = torch.zeros(K, d, dtype=torch.int64)
+    cnts = torch.zeros(K, dtype=torch.int64)
+    scale = torch.ldexp(torch.ones(d, dtype=torch.float64), col_exp.cpu().to(torch.float64))
+    if col_exp2 is not None:
+        e2 = col_exp2.cpu()
+        sc2 = torch.where(e2 > -200, torch.ldexp(torch.ones(d, dtype=torch.float64), (e2 - col_exp.cpu()).double()),
+                          torch.zeros(d, dtype=torch.float64))
+    for i in range(0, n, 1 << 17):
+        sl = slice(i, min(n, i + (1 << 17)))
+        xb = (X[rows[sl]] if rows is not None else X[sl]).double()
+        s = scale[None, :] * w[sl].double()[:, None] if w is not None else scale[None, :]
+        p = xb * s.float().double()
+        q = torch.round(p)
+        if col_exp2 is not None:
+            q = torch.round((p - q).float().double() * sc2[None, :])
+        c = torch.round(w[sl].double() * 2.0 ** cnt_exp) if w is not None else torch.ones(q.shape[0], dtype=torch.float64)
+        keep = lab[sl] >= 0
+        sums.index_add_(0, lab[sl][keep].long(), q[keep].to(torch.int64))
+        cnts.index_add_(0, lab[sl][keep].long(), c[keep].to(torch.int64))
+    return sums, cnts
+
+
+@pytest.mark.parametrize("shape,mode,labels", _SLAB_PARAMS)
+def test_slab_equals_the_exact_integer_sum(native, kvariant, shape, mode, labels):
+    """C.update / C.update_delta straight into the slab, against the integer sum of the
+    contributions formed on the CPU, bit for bit (integers: no tolerance).  one_label puts
+    n_chunks * 4100 rows into label K - 1, so every chunk adds more than 2 * FX_LIM times to one
+    label and flushes it mid-chunk at least twice -- through upd_flush_hot for the plain slice
+    kernel too, which the K-split routing keeps the other tests from reaching; mixed is random
+    labels with every third row unassigned (the global-atomic fallback, which has neither chunks
+    nor flushes, takes only those); delta moves every row from label 0 to label 1."""
+    C = native
+    dtype, d, K = _SLAB_SHAPES[shape]
+    dt = ops.dtype_code(dtype)
+    if shape == "f32_d8_global":
+        assert C.update_slice_width(dt, K, d, False) == 0
+    if mode.endswith("_slices"):
+        kvariant("update_ks", 0)
+        assert C.update_slice_width(dt, K, d, False) == 32
+    weighted = mode in ("weighted", "delta")   # (the LDS layout with signed 64-bit counts)
+    if mode == "delta":
+        n, nch = _slab_chunks(C, dt, K, d, True, 4100 // 2)   # 2 n list entries: 4100 a chunk
+    elif labels == "one_label":
+        n, nch = _slab_chunks(C, dt, K, d, weighted, 4100)
+        assert -(-n // nch) > 2 * FX_LIM
+    else:
+        n = 20_000 if shape == "f32_d8_global" else 50_000
+        nch = C.update_n_chunks(dt, K, d, n, weighted)
+    X, lab, w, rows = _slab_inputs(shape, labels, n)
+    Xd = X.to(DEV)
+    slab = torch.empty(nch * K * d, dtype=torch.int64, device=DEV)
+    cnt = torch.empty(nch * K, dtype=torch.int64, device=DEV)
+    if mode == "delta":   # every row moves from label 0 to label 1
+        lab = torch.ones(n, dtype=torch.int32)
+        col_exp, _ = ops.fixed_exps(Xd, None)
+        prev = torch.zeros(n, dtype=torch.int32, device=DEV)
+        lst = torch.empty((n + 8, 2), dtype=torch.int32, device=DEV)
+        count = torch.zeros(1, dtype=torch.int32, device=DEV)
+        labd = lab.to(DEV)
+        C.label_delta(labd, prev, lst, count)
+        assert int(count.item()) == n and torch.equal(prev, labd)
+        C.update_delta(Xd, labd, K, slab, cnt, nch, None, col_exp, 0, lst, count)
+        s1, c1 = _slab_reference(X, lab, K, col_exp)
+        ref_s, ref_c = s1.clone(), c1.clone()
+        ref_s[0], ref_c[0] = -s1[1], -c1[1]
+        assert int(ref_c[1]) == n
+    elif mode == "weighted":
+        col_exp, cnt_exp = ops.fixed_exps(Xd, w.to(DEV))
+        C.update(Xd, lab.to(DEV), K, slab, cnt, nch, w.to(DEV), col_exp, cnt_exp, False)
+        ref_s, ref_c = _slab_reference(X, lab, K, col_exp, w=w, cnt_exp=cnt_exp)
+    elif mode == "clamp":   # an in-range scale: nothing clamps, nothing is counted
+        col_exp, _ = ops.fixed_exps(Xd, None)
+        cc = torch.zeros(1, dtype=torch.int32, device=DEV)
+        C.update(Xd, lab.to(DEV), K, slab, cnt, nch, None, col_exp, 0, True, clamp_count=cc)
+        assert int(cc.item()) == 0
+        ref_s, ref_c = _slab_reference(X, lab, K, col_exp)
+    elif mode == "resid":   # the lo pass of two columns
+        col_exp, _ = ops.fixed_exps(Xd, None)
+        col_exp2 = torch.full_like(col_exp, -1000)
+        col_exp2[[3, 40]] = col_exp[[3, 40]] + 20
+        C.update(Xd, lab.to(DEV), K, slab, cnt, nch, None, col_exp, 0, False, col_exp2=col_exp2)
+        ref_s, ref_c = _slab_reference(X, lab, K, col_exp, col_exp2=col_exp2)
+        wide = int(ref_s[:, [3, 40]].abs().sum())   # (the other columns add nothing)
+        assert wide > 0 and int(ref_s.abs().sum()) == wide
+    elif mode.startswith("gather"):
+        col_exp, _ = ops.fixed_exps(Xd, None)
+        C.update(Xd, lab.to(DEV), K, slab, cnt, nch, None, col_exp, 0, False, rows=rows.to(DEV))
+        ref_s, ref_c = _slab_reference(X, lab, K, col_exp, rows=rows)
+    else:
+        col_exp, _ = ops.fixed_exps(Xd, None)
+        C.update(Xd, lab.to(DEV), K, slab, cnt, nch, None, col_exp, 0, False)
+        ref_s, ref_c = _slab_reference(X, lab, K, col_exp)
+    assert torch.equal(cnt.view(nch, K).sum(0).cpu(), ref_c)
+    assert torch.equal(slab.view(nch, K, d).sum(0).cpu(), ref_s)
+
+
+def test_update_refuses_strided_labels(native):
+    """labels[::2] of a 2N tensor is not contiguous: update reads labels densely, so it must refuse
+    them as update_delta does."""
+    C = native
+    n, d, K = 4096, 32, 8
+    dt = ops.dtype_code(torch.float32)
+    X = torch.randn(n, d, device=DEV)
+    lab = torch.zeros(2 * n, dtype=torch.int32, device=DEV)[::2]
+    nch = C.update_n_chunks(dt, K, d, n, False)
+    slab = torch.empty(nch * K * d, dtype=torch.int64, device=DEV)
+    cnt = torch.empty(nch * K, dtype=torch.int64, device=DEV)
+    col_exp, _ = ops.fixed_exps(X, None)
+    with pytest.raises(RuntimeError, match="labels must be contiguous int32"):
+        C.update(X, lab, K, slab, cnt, nch, None, col_exp, 0, False)

@@ -63,8 +63,18 @@ def test_launch_planning_under_asan_ubsan(tmp_path):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
 def test_width_dispatch_under_asan_ubsan(tmp_path):
     """csrc/dispatch.h for_width, for both element sizes: a case for exactly the widths
-    plan::assign_dpad returns over D = 1..1024, every other width in 1..2048 refused."""
+    plan::assign_dpad returns over D = 1..1024, every other width in 1..2048 refused; for_value:
+    a case for exactly the values of its list, every other value around it refused uncalled."""
     _run_harness(tmp_path, "width_fuzz")
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
+def test_fixed_point_cell_under_asan_ubsan(tmp_path):
+    """csrc/fx.h, the M-step's two-columns-per-u64 cell: n = 1, 2, FX_LIM - 1 and FX_LIM pairs at
+    +-2^20 (all four sign patterns) and random in [-2^20, 2^20], added modulo 2^64, decode to both
+    column sums exactly; FX_LIM + 1 adds of +2^20 do not (the no-wrap bound is tight); a label
+    flushed several times (stored first, added after) totals the same."""
+    _run_harness(tmp_path, "fx_fuzz")
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
