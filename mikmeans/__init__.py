@@ -13,7 +13,7 @@ human-in-the-loop k-means classroom game) rebuilt as a GPU engine:
 """
 import torch  # noqa: F401  -- torch's HIP runtime must be loaded before mikmeans._C
 
-from .api import (ClusterIndex, ClusterReport, KMeans, MiniBatchKMeans, build_index, cluster_exemplars, cluster_quantiles, cluster_report, fit,
+from .api import (ClusterIndex, ClusterReport, KMeans, MiniBatchKMeans, PQIndex, build_index, build_pq_index, cluster_exemplars, cluster_quantiles, cluster_report, fit,
                   fit_predict, kmeans_plusplus, predict, predict_topk)
 from .config import KMeansConfig
 from .parallel import Comm
@@ -44,4 +44,4 @@ def init(device: str | None = None, *, timeout_s: float = 600.0, verbose: bool =
 
 
 __all__ = ["KMeans", "MiniBatchKMeans", "fit", "predict", "predict_topk", "cluster_report", "ClusterReport",
-           "cluster_exemplars", "cluster_quantiles", "build_index", "ClusterIndex", "fit_predict", "kmeans_plusplus", "KMeansConfig", "Comm", "init", "__version__"]
+           "cluster_exemplars", "cluster_quantiles", "build_index", "ClusterIndex", "build_pq_index", "PQIndex", "fit_predict", "kmeans_plusplus", "KMeansConfig", "Comm", "init", "__version__"]

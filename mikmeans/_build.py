@@ -25,7 +25,7 @@ CSRC = PKG / "csrc"
 BUILD = PKG.parent / "build" / "native"
 ARCH = os.environ.get("MIKMEANS_ARCH", "gfx950")
 HIP_SOURCES = ["assign16.hip", "update.hip", "finalize.hip", "kpp.hip", "rows.hip", "transform.hip", "topk.hip",
-               "quality.hip", "exemplars.hip", "quantiles.hip", "ivf.hip", "range.hip", "deep.hip"]
+               "quality.hip", "exemplars.hip", "quantiles.hip", "ivf.hip", "range.hip", "deep.hip", "pq.hip"]
 BINDING = "binding.cpp"
 
 DEVICE_FLAGS = [

@@ -616,6 +616,175 @@ class ClusterIndex:
         return lims.cpu().numpy(), rows.cpu().numpy(), d.cpu().numpy()
 
 
+class PQIndex:
+    """The rows of a dataset grouped by their nearest centre and kept as product-quantiser codes
+    (IVF-PQ), from :meth:`KMeans.build_pq_index`: ``n_subvectors`` bytes a row instead of the row.
+    ``n_rows``: the rows given; ``n_indexed``: the rows in a list; ``list_sizes`` / ``offsets`` /
+    ``order`` / ``rows_of`` as in :class:`ClusterIndex`; ``codebooks`` float32 ``[n_subvectors, 256,
+    dsub]``; ``nbytes``: what the index keeps on its device, ``n M + 8 n + 8 (K + 1) + 4 M 256 dsub``.
+    One-rank jobs only; docs/PQ_INDEX.md has the definitions."""
+
+    FORMAT = "mikmeans-pq-index-v1"
+    TENSORS = "pq_index.safetensors"
+    META = "pq_index.json"
+
+    def __init__(self, model, index, row_start: int = 0):
+        self._model, self._index, self.row_start = model, index, int(row_start)
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._index.n)
+
+    @property
+    def n_indexed(self) -> int:
+        return int(self._index.offsets[-1])
+
+    @property
+    def n_subvectors(self) -> int:
+        return int(self._index.M)
+
+    @property
+    def offsets(self) -> torch.Tensor:
+        return self._index.offsets
+
+    @property
+    def list_sizes(self) -> torch.Tensor:
+        return self._index.offsets[1:] - self._index.offsets[:-1]
+
+    @property
+    def order(self) -> torch.Tensor:
+        return self._index.order[: int(self._index.offsets[-1])] + self.row_start
+
+    @property
+    def codebooks(self) -> torch.Tensor:
+        return self._index.codebooks
+
+    @property
+    def nbytes(self) -> int:
+        return self._index.nbytes
+
+    def rows_of(self, k: int) -> torch.Tensor:
+        """The row ids of cluster ``k``, ascending."""
+        K = self._index.K
+        if not 0 <= int(k) < K:
+            raise ValueError(f"rows_of needs 0 <= k < n_clusters ({K}), got k = {k}")
+        a, b = (int(v) for v in self._index.offsets[int(k) : int(k) + 2])
+        return self._index.order[a:b] + self.row_start
+
+    def search(self, Q, m: int, *, nprobe: int = 8, squared: bool = False):
+        """The ``m`` indexed rows of least asymmetric distance to every query among the lists of its
+        ``nprobe`` nearest centres: ``(rows [nq, m] int64, distances [nq, m] float32)``, nearest first
+        and equal distances by the lower row id; padding is row -1 and distance NaN.  ``1 <= m <= 32``
+        and ``1 <= nprobe <= n_clusters``.  A distance is the sum of ``n_subvectors`` table entries
+        (``ops.pq_search``; ``squared``: that sum, otherwise its square root), an estimate of the
+        distance to the row itself.  On the GPU: the top-``nprobe`` kernel, the transform kernel for
+        the tables and the scan of csrc/pq.hip, one workgroup per (query, probed list, split) with the
+        table in LDS; the memory plan (``memplan.plan_pq_search``) is checked against the HBM budget up
+        front.  Results are bitwise the same from run to run.  numpy in, numpy out."""
+        mdl, ix = self._model, self._index
+        m = int(m)
+        if not 1 <= m <= ops.INDEX_MAX_M:
+            raise ValueError(f"search needs 1 <= m <= {ops.INDEX_MAX_M}, got m = {m}")
+        c = mdl.cluster_centers_
+        K, nprobe = int(c.shape[0]), int(nprobe)
+        if not 1 <= nprobe <= K:
+            raise ValueError(f"search needs 1 <= nprobe <= n_clusters ({K}), got nprobe = {nprobe}")
+        if getattr(Q, "ndim", 2) != 2:
+            raise ValueError(f"Q must be 2-D [n_queries, n_features], got shape {tuple(Q.shape)}")
+        if ix.codes.is_cuda:
+            from .parallel import memplan
+
+            plan = memplan.plan_pq_search(ix.n, int(c.shape[1]), K, ix.M, ix.dtype, nq=int(Q.shape[0]), m=m, nprobe=nprobe)
+            plan.budget = memplan.hbm_budget(ix.codes.device) + sum(
+                plan.persistent[k] for k in ("codes", "order", "offsets", "codebooks"))   # (held already)
+            if not plan.fits:
+                raise memplan.HBMCapacityError(f"search: {plan.summary()} does not fit")
+        (keys,), was_numpy = mdl._row_blocks(Q, lambda Qt, pk: (ops.pq_search(ix, Qt, c, m, nprobe, pack=pk),))
+        rows, d2 = ops.index_decode(keys, row_start=self.row_start)
+        d = d2 if squared else d2.sqrt()
+        return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
+
+    def reconstruct(self, ids):
+        """float32 ``[len, n_features]``: every row id's centre plus its codewords; NaN rows for ids in
+        no list.  numpy in, numpy out."""
+        was_numpy = not torch.is_tensor(ids)
+        t = torch.as_tensor(np.asarray(ids)) if was_numpy else ids
+        if t.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+            raise ValueError(f"reconstruct takes integer row ids, got {t.dtype}")
+        ix = self._index
+        out = ops.pq_reconstruct(ix, t.reshape(-1).to(device=ix.codes.device, dtype=torch.int64) - self.row_start,
+                                 self._model.cluster_centers_)
+        return out.cpu().numpy() if was_numpy else out
+
+    def save(self, path):
+        """Write the index to the directory ``path``: ``pq_index.safetensors`` (its tensors and the
+        centres its rows were listed under) and ``pq_index.json`` (the format version and ``n``, ``K``,
+        ``D``, ``M``, ``dtype``, ``row_start``)."""
+        import json
+        import os
+        from pathlib import Path
+
+        from safetensors.torch import save_file
+
+        ix = self._index
+        path = Path(path)
+        path.mkdir(parents=True, exist_ok=True)
+        blobs = {k: v.detach().to("cpu").contiguous() for k, v in ix.tensors().items()}
+        blobs["centers"] = self._model.cluster_centers_.detach().to("cpu").contiguous()
+        tmp = path / (self.TENSORS + ".tmp")
+        save_file(blobs, str(tmp))
+        os.replace(tmp, path / self.TENSORS)
+        meta = {"format": self.FORMAT, "n": int(ix.n), "K": int(ix.K), "D": int(ix.D), "M": int(ix.M),
+                "dtype": "bfloat16" if ix.dtype == torch.bfloat16 else "float32", "row_start": int(self.row_start)}
+        tmpm = path / (self.META + ".tmp")
+        tmpm.write_text(json.dumps(meta))
+        os.replace(tmpm, path / self.META)
+        return path
+
+    @classmethod
+    def saved_at(cls, path) -> bool:
+        """Whether the directory ``path`` holds a saved PQ index."""
+        from pathlib import Path
+
+        return (Path(path) / cls.META).is_file() and (Path(path) / cls.TENSORS).is_file()
+
+    @classmethod
+    def load(cls, path, model, device=None) -> "PQIndex":
+        """The index :meth:`save` wrote, for ``model`` (whose fitted centres must be the saved ones, bit
+        for bit, and whose dtype the index's) on ``device`` (default: the model's).  It searches bit for
+        bit as the saved one on the same kind of device."""
+        import json
+        from pathlib import Path
+
+        from safetensors.torch import load_file
+
+        model._check_fitted()
+        comm = getattr(model, "comm", None) or get_comm()
+        if _allreduce(comm) is not None:
+            raise NotImplementedError("PQIndex.load is not available in a multi-rank job")
+        path = Path(path)
+        meta = json.loads((path / cls.META).read_text())
+        if meta.get("format") != cls.FORMAT:
+            raise ValueError(f"{path}: not a {cls.FORMAT} index (format {meta.get('format')!r})")
+        c = model.cluster_centers_
+        dev = torch.device(device) if device is not None else c.device
+        ts = load_file(str(path / cls.TENSORS))
+        saved_c = ts.pop("centers")
+        dtype = torch.bfloat16 if meta["dtype"] == "bfloat16" else torch.float32
+        if dtype != model.dtype:
+            raise ValueError(f"the index holds {dtype} rows, the model's dtype is {model.dtype}")
+        if saved_c.shape != c.shape or not torch.equal(saved_c, c.detach().to("cpu")):
+            raise ValueError("the model's cluster_centers_ are not the centres the index was saved under")
+        if dev.type != c.device.type:
+            raise ValueError(f"the index would load to {dev}, the model's centres are on {c.device}")
+        F = int(c.shape[1])
+        D = int(pad_columns(torch.empty((0, F), dtype=dtype)).shape[1]) if dev.type == "cuda" else F
+        ts = {k: v.to(dev) for k, v in ts.items()}
+        index = ops.PQRowIndex(int(meta["n"]), int(meta["K"]), D, int(meta["M"]), dtype, ts["codes"], ts["order"],
+                               ts["offsets"], ts["codebooks"])
+        return cls(model, index, int(meta["row_start"]))
+
+
 class _Params:
     """scikit-learn estimator protocol: ``get_params`` / ``set_params`` over the constructor's
     keyword arguments (so ``sklearn.base.clone``, pipelines and grid searches can rebuild an
@@ -898,6 +1067,54 @@ class _Serving(_Params):
         """The index :meth:`ClusterIndex.save` wrote to ``path``, on this model's device
         (:meth:`ClusterIndex.load`): the fitted centres must be the ones it was saved under."""
         return ClusterIndex.load(path, self)
+
+    def build_pq_index(self, X, n_subvectors: int = 16, *, train_rows: int = 65536, pq_max_iter: int = 25,
+                       seed: int | None = None, codebooks=None, block_rows: int | None = None) -> PQIndex:
+        """Index the rows of ``X`` by their nearest fitted centre and keep each as ``n_subvectors``
+        one-byte codes of its residual against that centre (product quantisation), for
+        :meth:`PQIndex.search`: ``n_subvectors`` bytes a row where :meth:`build_index` keeps the row.
+
+        ``n_subvectors`` in {8, 16, 32, 64} must divide the features.  The lists are
+        :meth:`build_index`'s (cosine models index unit rows; a row whose distance to its centre is NaN
+        or infinite takes an id and is in no list).  The 256 codewords of every sub-space are fitted by
+        this library's own :class:`KMeans` (``pq_max_iter`` iterations) on the residuals of
+        ``min(train_rows, n_indexed)`` listed rows drawn under ``seed`` (default: the model's), or
+        given as ``codebooks`` float32 ``[n_subvectors, 256, dsub]``; a code is the exact nearest
+        codeword (the top-1 kernel).  The index is bitwise the same from run to run and for any
+        ``block_rows``.  numpy or torch, host or device rows (host rows bound for a GPU model cross in
+        blocks).  One-rank jobs only; on a GPU the memory plan (``memplan.plan_pq_index``) is checked
+        against the HBM budget up front."""
+        self._check_fitted()
+        comm = getattr(self, "comm", None) or get_comm()
+        if _allreduce(comm) is not None:
+            raise NotImplementedError("build_pq_index is not available in a multi-rank job")
+        c = self.cluster_centers_
+        n, M = int(X.shape[0]), int(n_subvectors)
+        if getattr(X, "ndim", 0) != 2 or int(X.shape[1]) != int(c.shape[1]):
+            raise ValueError(f"build_pq_index takes rows [n, {int(c.shape[1])}], got shape {tuple(getattr(X, 'shape', ()))}")
+        ops.pq_check(int(c.shape[1]), M)
+        if n >= 1 << 32:
+            raise ValueError(f"build_pq_index takes fewer than 2^32 rows, got {n}")
+        if c.is_cuda:
+            from .parallel import memplan
+
+            plan = memplan.plan_pq_index(n, int(c.shape[1]), int(c.shape[0]), M, self.dtype, block_rows=block_rows,
+                                         train_rows=train_rows)
+            plan.budget = memplan.hbm_budget(c.device)
+            if not plan.fits:
+                raise memplan.HBMCapacityError(f"build_pq_index: {plan.summary()} does not fit")
+        if codebooks is not None:
+            codebooks = torch.as_tensor(np.asarray(codebooks) if not torch.is_tensor(codebooks) else codebooks,
+                                        dtype=torch.float32)
+        seed = int(getattr(self, "seed", 0) or 0) if seed is None else int(seed)
+        index = ops.pq_build(None, c, M, codebooks=codebooks, train_rows=train_rows, max_iter=pq_max_iter, seed=seed,
+                             block_rows=block_rows, n=n, blocks=lambda: self._host_blocks(X, block_rows))
+        return PQIndex(self, index, 0)
+
+    def load_pq_index(self, path) -> PQIndex:
+        """The index :meth:`PQIndex.save` wrote to ``path``, on this model's device
+        (:meth:`PQIndex.load`): the fitted centres must be the ones it was saved under."""
+        return PQIndex.load(path, self)
 
     def transform(self, X):
         """Euclidean distances to every centre, ``[n, K]`` (float32; for the cosine
@@ -1761,6 +1978,14 @@ def build_index(X, centers, dtype="float32") -> ClusterIndex:
     c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
     dev = c.device if torch.is_tensor(centers) else _default_device(None)
     return _GivenCenters(c.to(dev), resolve_dtype(dtype)).build_index(X)
+
+
+def build_pq_index(X, centers, n_subvectors: int = 16, dtype="float32", **kw) -> PQIndex:
+    """Index the rows of ``X`` under the given ``centers`` as ``n_subvectors`` one-byte codes a row
+    (``KMeans.build_pq_index`` without a model, which takes the other arguments)."""
+    c = torch.as_tensor(np.asarray(centers) if not torch.is_tensor(centers) else centers, dtype=torch.float32)
+    dev = c.device if torch.is_tensor(centers) else _default_device(None)
+    return _GivenCenters(c.to(dev), resolve_dtype(dtype)).build_pq_index(X, n_subvectors, **kw)
 
 
 def fit_predict(X, k: int, **kw):

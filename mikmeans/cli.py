@@ -224,7 +224,14 @@ def _search_index(a, km, comm):
     from .utils.io import load_points
 
     if a.index is not None:
-        index = km.load_index(a.index)
+        from . import PQIndex
+
+        if PQIndex.saved_at(a.index):          # whichever of the two formats the directory holds
+            if a.deep or a.radius is not None:
+                raise SystemExit(f"search: {a.index} holds a PQ index, which takes --top M without --deep")
+            index = km.load_pq_index(a.index)
+        else:
+            index = km.load_index(a.index)
         return index, index.n_rows
     X, n, start = load_points(a.input, comm.rank, comm.world)
     return km.build_index(X.to(comm.device)), n
@@ -242,6 +249,8 @@ def cmd_index(a) -> int:
 
     comm = _comm(a.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     km = KMeans.load(a.model, device=comm.device)
+    if a.pq is not None:
+        return _index_pq(a, km, comm)
     if a.input is not None:
         X, n, start = load_points(a.input, comm.rank, comm.world)
         index = km.build_index(X.to(comm.device))
@@ -258,6 +267,25 @@ def cmd_index(a) -> int:
     index.save(a.output)
     print(json.dumps({"n_rows": index.n_rows, "n_indexed": index.n_indexed, "added_first_id": first,
                       "removed": removed, "nbytes": index.nbytes}))
+    comm.close()
+    return 0
+
+
+def _index_pq(a, km, comm) -> int:
+    """``index --pq M`` (``KMeans.build_pq_index`` / ``PQIndex.save``): the rows of ``--input`` as M one-byte
+    codes a row, written to ``--output``.  Prints ``n_rows``, ``n_indexed``, ``n_subvectors`` and ``nbytes``."""
+    from .utils.io import load_points
+
+    if a.input is None or a.add is not None or a.remove is not None:
+        raise SystemExit("index: --pq builds from --input X; a PQ index takes no --add or --remove")
+    X, n, start = load_points(a.input, comm.rank, comm.world)
+    try:
+        index = km.build_pq_index(X.to(comm.device), a.pq, train_rows=a.train_rows)
+    except ValueError as e:
+        raise SystemExit(f"index: {e}")
+    index.save(a.output)
+    print(json.dumps({"n_rows": index.n_rows, "n_indexed": index.n_indexed, "n_subvectors": index.n_subvectors,
+                      "nbytes": index.nbytes}))
     comm.close()
     return 0
 
@@ -577,6 +605,9 @@ def build_parser():
     ip.add_argument("--input", help="the rows to index (.npy / .safetensors / .csv)")
     ip.add_argument("--add", metavar="X2", help="rows to add to the index (.npy / .safetensors / .csv)")
     ip.add_argument("--remove", metavar="IDS", help="row ids to take out of the index (.npy, integers)")
+    ip.add_argument("--pq", type=int, metavar="M", help="build a product-quantised index of M one-byte codes a row "
+                                                        "(KMeans.build_pq_index; M in 8, 16, 32, 64) from --input")
+    ip.add_argument("--train-rows", type=int, default=65536, help="with --pq: rows the codebooks are fitted on")
     ip.add_argument("--device")
     b = sub.add_parser("blobs", help="write a synthetic dataset")
     b.add_argument("--n", type=int, required=True)

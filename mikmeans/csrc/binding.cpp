@@ -447,6 +447,45 @@ void ivf_select(const Tensor& table, const Tensor& prefix, const Tensor& rank, c
   hip_check(mk::launch_ivf_select(a, stream()), "ivf_select");
 }
 
+// The scan of a product-quantised index (csrc/pq.hip): out [npairs, splits, m] keys
+void pq_scan(const Tensor& codes, const Tensor& order, const Tensor& offsets, const Tensor& lut, const Tensor& probes,
+             int64_t splits, const Tensor& out) {
+  check_cuda(codes, "codes");
+  TORCH_CHECK(codes.dim() == 2 && codes.scalar_type() == at::kByte && codes.is_contiguous(),
+              "mikmeans: codes must be contiguous uint8 [n, M]");
+  const int64_t n = codes.size(0), M = codes.size(1), K = offsets.numel() - 1;
+  TORCH_CHECK(mk::pq_subvectors_ok((int)M), "mikmeans: pq_scan takes M in {8, 16, 32, 64}, got ", M);
+  TORCH_CHECK(K >= 1, "mikmeans: offsets must be [K + 1]");
+  TORCH_CHECK(n < (int64_t(1) << 32), "mikmeans: pq_scan takes fewer than 2^32 rows");
+  check_i64(order, "order", n);
+  check_i64(offsets, "offsets", K + 1);
+  TORCH_CHECK(lut.dim() == 3 && lut.size(1) == M && lut.size(2) == mk::PQ_KSUB, "mikmeans: lut must be [npairs, M, 256]");
+  const int64_t npairs = lut.size(0);
+  check_f32(lut, "lut", npairs * M * mk::PQ_KSUB);
+  check_i32(probes, "probes", npairs);
+  TORCH_CHECK(probes.numel() == npairs, "mikmeans: probes must hold one list per pair");
+  TORCH_CHECK(splits >= 1 && splits <= mk::PQ_MAX_SPLITS, "mikmeans: pq_scan needs 1 <= splits <= ", mk::PQ_MAX_SPLITS,
+              ", got ", splits);
+  TORCH_CHECK(out.dim() == 3 && out.size(0) == npairs && out.size(1) == splits, "mikmeans: out must be [npairs, splits, m]");
+  const int64_t m = out.size(2);
+  TORCH_CHECK(m >= 1 && m <= mk::TOPK_MAX, "mikmeans: pq_scan needs 1 <= m <= ", mk::TOPK_MAX, ", got m = ", m);
+  check_i64(out, "out", npairs * splits * m);
+  TORCH_CHECK(mk::pq_grid(npairs, (int)splits) > 0 || npairs == 0, "mikmeans: too many pairs for one pq_scan launch");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(codes.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(lut.data_ptr()) % 16 == 0,
+              "mikmeans: codes and lut must be 16-B aligned");
+  const int dev = codes.get_device();
+  for (const Tensor* t : {&order, &offsets, &lut, &probes, &out})
+    TORCH_CHECK(t->get_device() == dev, "mikmeans: pq_scan tensors must share a device");
+  mk::PqScanArgs a;
+  a.codes = codes.data_ptr<uint8_t>(); a.n = n; a.order = order.data_ptr<int64_t>();
+  a.offsets = offsets.data_ptr<int64_t>(); a.K = (int)K; a.M = (int)M;
+  a.lut = lut.data_ptr<float>(); a.probes = probes.data_ptr<int32_t>(); a.npairs = npairs;
+  a.m = (int)m; a.splits = (int)splits;
+  a.out = reinterpret_cast<long long*>(out.data_ptr<int64_t>());
+  hip_check(mk::launch_pq_scan(a, stream()), "pq_scan");
+}
+
 void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {
   TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUALITY_WORDS, "mikmeans: table must be [K, ",
               mk::QUALITY_WORDS, "]");
@@ -1206,6 +1245,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("table"), py::arg("prefix"), py::arg("rank"), py::arg("hits"), py::arg("cand"), py::arg("m"),
         py::arg("pass"));
   m.attr("IVF_DEEP_MAX_M") = mk::IVF_DEEP_MAX_M;
+  m.def("pq_scan", &pq_scan,
+        "the m nearest rows by asymmetric distance of every ((query, probed list) pair, split) of a product-quantised "
+        "index as (sum bits << 32 | row) keys, the pair's table held in LDS",
+        py::arg("codes"), py::arg("order"), py::arg("offsets"), py::arg("lut"), py::arg("probes"), py::arg("splits"),
+        py::arg("out"));
+  m.def("pq_scan_splits", [](int64_t npairs) { return mk::pq_scan_splits(npairs); },
+        "workgroups that share one (query, probed list) pair of a pq_scan over npairs pairs");
+  m.def("pq_lds_bytes", [](int64_t M, int64_t m_) { return mk::pq_lds_bytes((int)M, (int)m_); });
+  m.attr("PQ_MAX_SPLITS") = mk::PQ_MAX_SPLITS;
   m.def("quality_accumulate", &quality_accumulate,
         "add the top-2 output's per-cluster quality words into table [K, QUALITY_WORDS] (integer atomics)",
         py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("path") = -1);

@@ -9,6 +9,7 @@
 
 #include "dispatch.h"   // for_width: the (dtype, padded width) switch of every launcher that has one
 #include "fold.h"       // the frame constants of the per-cluster folds (FOLD_*)
+#include "pqplan.h"     // the launch planning of the product-quantised scan (PQ_*, pq_scan_splits)
 #include "walk.h"       // the work item of a walk over an index's lists, its grid bound, walk_blocks
 
 namespace mk {
@@ -258,6 +259,28 @@ struct IvfSelectArgs {
   int64_t nq; int m; int pass;
 };
 hipError_t launch_ivf_select(const IvfSelectArgs& a, hipStream_t s);
+
+// ---- the scan of a product-quantised index (csrc/pq.hip) -----------------------------------
+// Pair p = query * nprobe + probe scans list probes[p] of an index whose rows are M-byte codes
+// (codes [n, M], the rows of order position after position) against its own table lut[p] [M][256]:
+// a row's distance is lut[p][0][c0] + lut[p][1][c1] + ... in that order, float32.  `splits`
+// workgroups share a pair (csrc/pqplan.h) and each writes its m smallest keys (sum bits << 32 |
+// row), ascending, into out[p][split][0..m); IVF_EMPTY_KEY where it met fewer than m rows.
+// M in {8, 16, 32, 64}, 1 <= m <= TOPK_MAX, 1 <= splits <= PQ_MAX_SPLITS; codes and lut 16-byte
+// aligned.  Bitwise the same on every launch.
+struct PqScanArgs {
+  const uint8_t* codes; int64_t n;   // [n, M]
+  const int64_t* order;              // [n] row ids, list after list
+  const int64_t* offsets;            // [K + 1] list starts in order
+  int K; int M;
+  const float* lut;                  // [npairs, M, 256]
+  const int32_t* probes;             // [npairs] every pair's list
+  int64_t npairs;
+  int m; int splits;
+  long long* out;                    // [npairs, splits, m]
+};
+static_assert(PQ_MAX_M == TOPK_MAX && PQ_NW == 4, "csrc/pqplan.h mirrors the register-list kernels' constants");
+hipError_t launch_pq_scan(const PqScanArgs& a, hipStream_t s);
 
 // ---- per-cluster quality table (csrc/quality.hip) ----------------------------------------
 // Folds launch_topk's output (m = 1 or 2) into table[K][QUALITY_WORDS] (u64, only ever added

@@ -501,3 +501,8 @@ from .index import *  # noqa: E402,F401,F403
 from .index import __all__ as _index_all  # noqa: E402
 
 __all__ += _index_all
+
+from .pq import *  # noqa: E402,F401,F403
+from .pq import __all__ as _pq_all  # noqa: E402
+
+__all__ += _pq_all

@@ -477,3 +477,65 @@ def index_select(table: torch.Tensor, prefix: torch.Tensor, rank: torch.Tensor, 
     R = torch.where(has, R - below, zero)
     hits = torch.where(has, found - 1 - R + table.gather(1, b[:, None])[:, 0], zero)
     return P.to(torch.int32), R, hits, cand
+
+
+# ---- product-quantised index (csrc/pq.hip, csrc/pqplan.h) ----------------------------------------
+PQ_SUBVECTORS = (8, 16, 32, 64)     # csrc/pqplan.h pq_subvectors_ok
+PQ_KSUB = 256                       # codewords of a sub-space
+PQ_MAX_SPLITS = 8                   # csrc/pqplan.h PQ_MAX_SPLITS
+
+
+def pq_encode(R: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """Codes uint8 ``[n, M]``: sub-vector j's nearest codeword by :func:`topk` (m = 1)."""
+    M, _, dsub = codebooks.shape
+    codes = torch.empty((R.shape[0], M), dtype=torch.uint8, device=R.device)
+    for j in range(M):
+        codes[:, j] = topk(R[:, j * dsub : (j + 1) * dsub], codebooks[j].to(R.device), 1)[0][:, 0].to(torch.uint8)
+    return codes
+
+
+def pq_lut(RQ: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """Tables float32 ``[npairs, M, 256]``: sub-vector j's squared distances to the quantised codewords,
+    in the form :func:`mikmeans.ops.transform` takes off the GPU (``cdist``, squared)."""
+    M, _, dsub = codebooks.shape
+    lut = torch.empty((RQ.shape[0], M, PQ_KSUB), dtype=torch.float32, device=RQ.device)
+    for j in range(M):
+        d = torch.cdist(RQ[:, j * dsub : (j + 1) * dsub].to(torch.float32),
+                        quantize_centers(codebooks[j].to(RQ.device), RQ.dtype))
+        lut[:, j, :] = d * d
+    return lut
+
+
+def pq_adc(lut: torch.Tensor, pair: torch.Tensor, codes: torch.Tensor) -> torch.Tensor:
+    """``lut[pair, 0, codes[:, 0]] + lut[pair, 1, codes[:, 1]] + ...``: float32 adds in sub-space order
+    (csrc/pq.hip pq_adc).  ``pair`` int64 ``[nq, rows]``, ``codes`` uint8 ``[rows, M]``."""
+    c = codes.to(torch.int64)
+    acc = lut[pair, 0, c[None, :, 0]]
+    for j in range(1, codes.shape[1]):
+        acc = torch.add(acc, lut[pair, j, c[None, :, j]])
+    return acc
+
+
+def pq_scan(index, lut: torch.Tensor, probes: torch.Tensor, m: int) -> torch.Tensor:
+    """Sorted search keys int64 ``[nq, m]`` (``ADC bits << 32 | row``, ``IVF_EMPTY_KEY`` padded) of the
+    queries whose pairs ``q * nprobe + j`` have the tables ``lut`` and the lists ``probes`` ``[nq, nprobe]``."""
+    K, dev = index.K, lut.device
+    nq, nprobe = probes.shape
+    sizes = index.offsets[1:] - index.offsets[:-1]
+    nv = int(index.offsets[K])
+    lid = torch.repeat_interleave(torch.arange(K, dtype=torch.int64, device=dev), sizes)
+    rid, codes = index.order[:nv], index.codes[:nv]
+    keys = torch.full((nq, m), IVF_EMPTY_KEY, dtype=torch.int64, device=dev)
+    rows = max(1, (1 << 22) // max(nv, 1))
+    for s in range(0, nq, rows):
+        pr = probes[s : s + rows].to(torch.int64)
+        nb = pr.shape[0]
+        rank = torch.full((nb, K), -1, dtype=torch.int64, device=dev)
+        rank.scatter_(1, pr, torch.arange(nprobe, dtype=torch.int64, device=dev)[None, :].expand(nb, nprobe))
+        of = rank[:, lid]                                               # [nb, nv]: the probe rank of the row's list
+        pair = (torch.arange(s, s + nb, dtype=torch.int64, device=dev)[:, None] * nprobe + of.clamp(min=0))
+        d = pq_adc(lut, pair, codes)
+        key = (d.contiguous().view(torch.int32).to(torch.int64) << 32) | rid[None, :]
+        key = torch.where(of >= 0, key, IVF_EMPTY_KEY).sort(dim=1).values[:, :m]
+        keys[s : s + rows, : key.shape[1]] = key
+    return keys

@@ -538,6 +538,71 @@ def plan_index_search_deep(n: int, D: int, K: int, dtype="bfloat16", *, nq: int,
     return MemoryPlan("index-search-deep", n, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
 
 
+PQ_KSUB = 256                    # ops.PQ_KSUB: codewords of a sub-space
+PQ_SCAN_BYTES = 1 << 30          # ops.PQ_SCAN_BYTES
+PQ_ENCODE_ROWS = 1 << 18         # ops.PQ_ENCODE_ROWS
+PQ_MAX_SPLITS = 8                # csrc/pqplan.h
+
+
+def pq_block_queries(M: int, m: int, nprobe: int, F: int, splits: int = PQ_MAX_SPLITS) -> int:
+    """ops.pq_block_queries: queries per block of a PQ search."""
+    return max(1, PQ_SCAN_BYTES // (int(nprobe) * (int(M) * PQ_KSUB * 4 + 8 * int(F) + 16 * int(splits) * int(m))))
+
+
+def _pq_held(n: int, D: int, K: int, M: int) -> dict:
+    """What a PQ index keeps (ops.PQRowIndex.tensors; the codes carry one spare row while they are built)."""
+    return {"codes": _r((n + 1) * M), "order": _r(n * 8), "offsets": _r((K + 1) * 8),
+            "codebooks": _r(M * PQ_KSUB * (D // M) * 4)}
+
+
+def plan_pq_index(n: int, D: int, K: int, M: int, dtype="bfloat16", *, block_rows: int | None = None,
+                  train_rows: int = 65536) -> MemoryPlan:
+    """A product-quantised index of ``n`` rows in ``M`` sub-vectors (ops.pq_build /
+    KMeans.build_pq_index): what it keeps -- ``M`` bytes of codes a row, ``order``, ``offsets`` and the
+    codebooks -- and the build's scratch: every row's list and position and the partition's cells
+    throughout; one block of top-1 output for the lists; the training sample with its gathered rows
+    and the sub-space fit's buffers; one pass of residuals (float32 and the rows' dtype), their padded
+    sub-vectors, top-1 output and codes for the encoding."""
+    es = esize_of(dtype)
+    Dp = padded_cols(D, es)
+    dsub = D // M
+    dsp = padded_cols(dsub, es)
+    p = _pq_held(n, D, K, M)
+    held = {"labels": _r(n * 4), "row_pos": _r(n * 8), "partition_cells": _r(K * partition_blocks(n, K) * 8)}
+    B = min(n, int(block_rows) if block_rows else TOPK_BLOCK_ROWS)
+    T = min(n, int(train_rows))
+    E = min(n, int(block_rows) if block_rows else PQ_ENCODE_ROWS, PQ_ENCODE_ROWS)
+    tr = {"lists": {**held, "top1_idx": _r(B * 4), "top1_d2": _r(B * 4), "top1_xn": _r(B * 4), "top1_labels": _r(B * 4)},
+          "train": {**held, "sample_ids": _r(3 * T * 8), "sample_rows": _r(T * Dp * es), "sample_f32": _r(2 * T * D * 4),
+                    "residuals": _r(2 * T * D * es), "slice": _r(T * dsp * es), "slice_norms": _r(T * 4),
+                    "slice_labels": _r(2 * T * 4), "slice_dist": _r(T * 4),
+                    "fit_sums": _r(256 * (PQ_KSUB * dsp + PQ_KSUB) * 8)},
+          "encode": {**held, "residual_f32": _r(2 * E * D * 4), "residuals": _r(E * D * es), "slice": _r(E * dsp * es),
+                     "top1_idx": _r(E * 4), "top1_d2": _r(E * 4), "top1_xn": _r(E * 4), "codes_block": _r(E * M),
+                     "positions": _r(2 * E * 8), "codebook_packs": _r(M * PQ_KSUB * max(dsp, 32) * es * 2)}}
+    return MemoryPlan("pq-index", n, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
+
+
+def plan_pq_search(n: int, D: int, K: int, M: int, dtype="bfloat16", *, nq: int, m: int, nprobe: int) -> MemoryPlan:
+    """A PQ search (ops.pq_search) of ``nq`` queries for ``m`` rows each over ``nprobe`` lists: the index
+    and the result, and per block of queries (``pq_block_queries``) the probes, the pairs' residuals
+    (float32 and the rows' dtype), one sub-space's padded slice and distances, the tables (``M`` KiB a
+    pair) and the keys (``splits * m`` a pair) with the sort's copies."""
+    es = esize_of(dtype)
+    Dp = padded_cols(D, es)
+    dsp = padded_cols(D // M, es)
+    p = {**_pq_held(n, D, K, M), "result_keys": _r(nq * m * 8)}
+    B = min(int(nq), pq_block_queries(M, m, nprobe, D))
+    pairs = B * int(nprobe)
+    keys = _r(pairs * PQ_MAX_SPLITS * m * 8)
+    tr = {"block": {"queries": _r(B * Dp * es), "query_norms": _r(B * 4), "probes": _r(2 * pairs * 4),
+                    "probe_d2": _r(pairs * 4), "probe_centres": _r(pairs * D * 4), "residual_f32": _r(pairs * D * 4),
+                    "residuals": _r(pairs * D * es), "slice": _r(pairs * dsp * es), "slice_norms": _r(pairs * 4),
+                    "slice_d2": _r(pairs * PQ_KSUB * 4), "tables": _r(pairs * M * PQ_KSUB * 4), "keys": keys,
+                    "sorted_keys": keys, "sort_order": keys, "block_keys": _r(B * m * 8)}}
+    return MemoryPlan("pq-index-search", n, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
+
+
 # ------------------------------------------------------------------------ budget
 def hbm_budget(device=None) -> int:
     """Bytes a fit on ``device`` may allocate: ``MIKMEANS_HBM_BYTES`` when set, else the free
