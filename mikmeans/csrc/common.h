@@ -59,6 +59,16 @@ __device__ __forceinline__ void unpack16(const u32x4& w, float* o, float*) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) o[i] = __uint_as_float(w[i]);
 }
+// A 16-byte piece's share of the canonical row norm (finalize.hip row_sqnorm_kernel): acc chained
+// through one fma per element, x^2 + acc, in element order.
+template <typename T>
+__device__ __forceinline__ float piece_sqnorm(const u32x4& w, float acc) {
+  float f[Elem<T>::V];
+  unpack16(w, f, (T*)nullptr);
+#pragma unroll
+  for (int e = 0; e < Elem<T>::V; ++e) acc = __builtin_fmaf(f[e], f[e], acc);
+  return acc;
+}
 
 // ---------------------------------------------------------------------------
 // LDS-DMA: each lane copies 16 B from its own global address to
@@ -306,6 +316,12 @@ __device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
     k1 += 0xBB67AE85u;
   }
   return c;
+}
+// The 53-bit uniform in [0, 1) of a block: its first two words as one 64-bit word, >> 11, * 2^-53
+// (rows.hip: the row sampler and the k-means|| flags; NumPy mirror in mikmeans/data/sampler.py).
+__device__ __forceinline__ double philox_u53(const U4& r) {
+  const uint64_t w = ((uint64_t)r.y << 32) | r.x;
+  return (double)(w >> 11) * 0x1p-53;
 }
 __device__ __forceinline__ float u01_open0(uint32_t v) { return ((v >> 8) + 1) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ float u01(uint32_t v) { return (v >> 8) * (1.0f / 16777216.0f); }

@@ -1,4 +1,5 @@
-// mikmeans — the one (dtype, padded width) dispatch of the MFMA distance kernels.
+// mikmeans — the one (dtype, padded width) dispatch of the MFMA distance kernels, and the dtype,
+// flag and value dispatches of every other launcher.
 //
 // Host only and free of HIP types, like plan.h, so tests/native/width_fuzz.cpp builds it with
 // g++ -fsanitize=address,undefined.  There is no width list here: a kernel is instantiated for
@@ -55,6 +56,21 @@ inline int for_width(int dtype, int dpad, F&& f) {
   if (dtype == WIDTH_BF16) return detail::for_width_in<uint16_t>(dpad, f, seq);
   return detail::for_width_in<float>(dpad, f, seq);
 }
+
+// The row type alone: f(TypeTag<T>{}) and its result, bf16 for WIDTH_BF16 and float for any other
+// dtype, as for_width reads it.  And a run-time flag as a constant: f(std::bool_constant<B>{}).
+template <typename F>
+inline int for_type(int dtype, F&& f) {
+  if (dtype == WIDTH_BF16) return (int)f(TypeTag<uint16_t>{});
+  return (int)f(TypeTag<float>{});
+}
+template <typename F>
+inline int for_flag(bool b, F&& f) {
+  if (b) return (int)f(std::bool_constant<true>{});
+  return (int)f(std::bool_constant<false>{});
+}
+// Elements of a 16-byte piece of a row of that type (common.h Elem<T>::V, for host code).
+constexpr int dtype_vec(int dtype) { return dtype == WIDTH_BF16 ? 8 : 4; }
 
 // The same for one run-time value out of an explicit list: f(std::integral_constant<int, V>{})
 // for the V that equals v, and its result; hipErrorInvalidValue (1), without calling f, for a

@@ -83,16 +83,18 @@ __global__ __launch_bounds__(256) void finalize_kernel(FinalizeArgs a) {
 
 hipError_t launch_finalize(const FinalizeArgs& a, hipStream_t s) {
   const unsigned nb = (unsigned)((a.Kpad + 31) / 32);
-  if (a.dtype == DT_BF16) hipLaunchKernelGGL(finalize_kernel<uint16_t>, dim3(nb), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(finalize_kernel<float>, dim3(nb), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return (hipError_t)for_type(a.dtype, [&](auto t) {
+    hipLaunchKernelGGL(finalize_kernel<typename decltype(t)::type>, dim3(nb), dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------
 // K1: xn[i] = sum_d x[i,d]^2 (f32).  16 lanes per row, 16-B loads.  The order is canonical --
-// lane s chains fmas over the elements of pieces s, s+16, s+32, ... in turn, then a 16-lane
-// butterfly (1, 2, 4, 8; common.h sum16_xor) -- and shared with every other producer of row norms (the fused
-// column-statistics pass below, csrc/rows.hip sample_rows), so all of them give the same bits.
+// lane s chains fmas over the elements of pieces s, s+16, s+32, ... in turn (common.h piece_sqnorm),
+// then a 16-lane butterfly (1, 2, 4, 8; common.h sum16_xor) -- and shared with every other producer
+// of row norms (the fused column-statistics pass below, csrc/rows.hip sample_rows and row_normalize),
+// so all of them give the same bits.
 template <typename T>
 __global__ __launch_bounds__(256) void row_sqnorm_kernel(const T* __restrict__ X, int64_t N, int D,
                                                          int64_t ldx, float* __restrict__ out) {
@@ -103,13 +105,7 @@ __global__ __launch_bounds__(256) void row_sqnorm_kernel(const T* __restrict__ X
     const T* row = X + i * ldx;
     float acc = 0.f;
     if ((D % V) == 0) {
-      for (int c = sub * V; c < D; c += 16 * V) {
-        const u32x4 w = *(const u32x4*)(row + c);
-        float f[V];
-        unpack16(w, f, (T*)nullptr);
-#pragma unroll
-        for (int e = 0; e < V; ++e) acc = __builtin_fmaf(f[e], f[e], acc);
-      }
+      for (int c = sub * V; c < D; c += 16 * V) acc = piece_sqnorm<T>(*(const u32x4*)(row + c), acc);
     } else {
       for (int c = sub; c < D; c += 16) { const float f = Elem<T>::to_f32(row[c]); acc = __builtin_fmaf(f, f, acc); }
     }
@@ -123,13 +119,11 @@ hipError_t launch_row_sqnorm(int dtype, const void* X, int64_t N, int D, int64_t
   if (N <= 0) return hipSuccess;
   int64_t nb = (N + 15) / 16;
   if (nb > 8192) nb = 8192;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(row_sqnorm_kernel<uint16_t>, dim3((unsigned)nb), dim3(256), 0, s,
-                       (const uint16_t*)X, N, D, ldx, out);
-  else
-    hipLaunchKernelGGL(row_sqnorm_kernel<float>, dim3((unsigned)nb), dim3(256), 0, s,
-                       (const float*)X, N, D, ldx, out);
-  return hipGetLastError();
+  return (hipError_t)for_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(row_sqnorm_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, (const T*)X, N, D, ldx, out);
+    return hipGetLastError();
+  });
 }
 
 // Packed 16-bit helpers, written out (left to itself the compiler turns min(y, 1) per half into
@@ -454,18 +448,25 @@ static int colstat_cap(int D) {
   return (int)(fit < 2048 ? 2048 : fit > COLSTAT_BLOCKS ? COLSTAT_BLOCKS : fit);
 }
 
+// One launch over NP (<= 64) 16-byte pieces of N rows: L lanes per row (the pieces rounded up to a
+// power of two) and its blocks.  Each block streams its rows with 4 loads in flight per lane
+// (colstat_cap: one resident round of longer-lived blocks, 768, measured 7.6 % slower than 2048,
+// profiles/r6_04_ab_colstats_d128.log).
+static int64_t colstat_grid(int64_t N, int NP, int D, int& L) {
+  L = plan::pow2_at_least(NP, 64);
+  const int R = 256 / L;
+  const int64_t nb = (N + R - 1) / R;
+  return nb > colstat_cap(D) ? colstat_cap(D) : nb;
+}
+
 // Blocks of the widest launch launch_col_absmax makes for N rows of D columns: the rows of
 // fpart it writes (the caller's allocation; ADVICE r5: sized to N, not to COLSTAT_BLOCKS).
 int colstat_rows(int dtype, int64_t N, int D) {
-  const int V = dtype == DT_BF16 ? 8 : 4;
-  const int NPT = D / V;
+  const int NPT = D / dtype_vec(dtype);
   int64_t rows = 0;
   for (int p0 = 0; p0 < NPT; p0 += 64) {
-    const int NP = NPT - p0 < 64 ? NPT - p0 : 64;
-    int L = 1;
-    while (L < NP) L *= 2;
-    int64_t nb = (N + 256 / L - 1) / (256 / L);
-    if (nb > colstat_cap(D)) nb = colstat_cap(D);
+    int L;
+    const int64_t nb = colstat_grid(N, NPT - p0 < 64 ? NPT - p0 : 64, D, L);
     rows = nb > rows ? nb : rows;
   }
   return (int)rows;
@@ -474,7 +475,7 @@ int colstat_rows(int dtype, int64_t N, int D) {
 hipError_t launch_col_absmax(int dtype, const void* X, int64_t N, int D, int64_t ldx, uint32_t* out,
                              hipStream_t s, double* fstats, unsigned long long* nnz, int* lowbit, double* fpart,
                              float* xn) {
-  const int V = dtype == DT_BF16 ? 8 : 4;
+  const int V = dtype_vec(dtype);
   const int NPT = D / V;
   if (N <= 0 || D % V || NPT < 1) return N <= 0 ? hipSuccess : hipErrorInvalidValue;
   if ((fstats != nullptr) != (nnz != nullptr) || (fstats != nullptr) != (lowbit != nullptr) ||
@@ -485,34 +486,29 @@ hipError_t launch_col_absmax(int dtype, const void* X, int64_t N, int D, int64_t
   for (int p0 = 0; p0 < NPT; p0 += 64) {
     const int NP = NPT - p0 < 64 ? NPT - p0 : 64;
     const int64_t c0 = (int64_t)p0 * V;
-    int L = 1;
-    while (L < NP) L *= 2;
-    const int R = 256 / L;
-    int64_t nb = (N + R - 1) / R;
-    // each block streams its rows with 4 loads in flight per lane (colstat_cap: one resident
-    // round of longer-lived blocks, 768, measured 7.6 % slower than 2048,
-    // profiles/r6_04_ab_colstats_d128.log)
-    if (nb > colstat_cap(D)) nb = colstat_cap(D);
-    const dim3 g((unsigned)nb), b(256);
+    int L;
+    const dim3 g((unsigned)colstat_grid(N, NP, D, L)), b(256);
     double* fp = fpart ? fpart + c0 : nullptr;
     unsigned long long* nz = nnz ? nnz + c0 : nullptr;
     int* lb = lowbit ? lowbit + c0 : nullptr;
-#define MK_COLSTAT(TT, ST, NR, LT)                                                                              \
-  hipLaunchKernelGGL((col_absmax_kernel<TT, ST, NR, LT>), g, b, 0, s, (const TT*)X + c0, N, NP, L, ldx, out + c0, \
-                     fp, (int64_t)D, nz, lb, xn)
-    if (dtype == DT_BF16) {
-      if (fstats) {
-        if (xn && L == 16) MK_COLSTAT(uint16_t, true, true, 16);
-        else if (xn) MK_COLSTAT(uint16_t, true, true, 0);
-        else MK_COLSTAT(uint16_t, true, false, 0);
-      } else {
-        if (xn) MK_COLSTAT(uint16_t, false, true, 0); else MK_COLSTAT(uint16_t, false, false, 0);
-      }
-    } else {
-      if (fstats) { if (xn) MK_COLSTAT(float, true, true, 0); else MK_COLSTAT(float, true, false, 0); }
-      else { if (xn) MK_COLSTAT(float, false, true, 0); else MK_COLSTAT(float, false, false, 0); }
-    }
-#undef MK_COLSTAT
+    const int e = for_type(dtype, [&](auto t) {
+      using T = typename decltype(t)::type;
+      return for_flag(fstats != nullptr, [&](auto st) {
+        return for_flag(xn != nullptr, [&](auto nr) {
+          constexpr bool ST = decltype(st)::value, NR = decltype(nr)::value;
+          auto launch = [&](auto lt) {
+            hipLaunchKernelGGL((col_absmax_kernel<T, ST, NR, decltype(lt)::value>), g, b, 0, s, (const T*)X + c0, N,
+                               NP, L, ldx, out + c0, fp, (int64_t)D, nz, lb, xn);
+            return hipGetLastError();
+          };
+          // (lanes at compile time: built for the one case that pays, see col_absmax_kernel's LT)
+          if constexpr (sizeof(T) == 2 && ST && NR)
+            if (L == 16) return launch(std::integral_constant<int, 16>{});
+          return launch(std::integral_constant<int, 0>{});
+        });
+      });
+    });
+    if (e) return (hipError_t)e;
   }
   if (fstats)
     hipLaunchKernelGGL(colstat_reduce_kernel, dim3((unsigned)(3 * D)), dim3(256), 0, s, fpart, (int64_t)3 * D,

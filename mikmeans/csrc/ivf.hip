@@ -6,7 +6,8 @@
 //    ascending inside a label, offsets = where each label's rows start (the stable sort of the
 //    labels and the cumulative bincount).  Count, scan, scatter in the style of the compaction
 //    kernels of csrc/rows.hip: a workgroup counts its contiguous rows per label in LDS, one
-//    workgroup scans the [K][blocks] counts (label-major, so a label's blocks follow each other),
+//    workgroup scans the [K][blocks] counts (label-major, so a label's blocks follow each other;
+//    block.h scan_slices),
 //    and the scatter pass recounts per wave, turns the [4 waves][K] counters into running
 //    positions (block base + the waves before) and walks its rows again: the lanes of a wave that
 //    share a label are found by ballots, a lane's rank among them is the mbcnt of that ballot and
@@ -28,6 +29,7 @@
 //    for (query, row) with the rows packed as centres: the one tile step of tile.h (negatives to
 //    +0, NaN and +inf kept, so a query with a NaN or infinite coordinate finds no row at distance
 //    0).
+#include "block.h"
 #include "dispatch.h"
 #include "pack.h"
 #include "topk.h"
@@ -68,34 +70,13 @@ __global__ __launch_bounds__(PT_T) void partition_count_kernel(const int32_t* __
 // label k's first block, offsets[K] = the total.  One workgroup, fixed order.
 __global__ __launch_bounds__(1024) void partition_scan_kernel(int64_t* __restrict__ cells, int64_t nb, int K,
                                                               int64_t* __restrict__ offsets) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t tot;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int64_t total = (int64_t)K * nb;
-  int64_t carry = 0;
-  for (int64_t s0 = 0; s0 < total; s0 += 1024) {
-    const int64_t i = s0 + threadIdx.x;
-    const int64_t v = i < total ? cells[i] : 0;
-    int64_t incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int64_t u = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += u;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    for (int j = 0; j < w; ++j) incl += wsum[j];
-    if (threadIdx.x == 1023) tot = incl;
-    if (i < total) {
-      const int64_t excl = carry + incl - v;
-      cells[i] = excl;
-      if (i % nb == 0) offsets[i / nb] = excl;
-    }
-    __syncthreads();
-    carry += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) offsets[K] = carry;
+  const int64_t total = scan_slices<1024>(
+      (int64_t)K * nb, [&](int64_t i) { return cells[i]; },
+      [&](int64_t i, int64_t excl) {
+        cells[i] = excl;
+        if (i % nb == 0) offsets[i / nb] = excl;
+      });
+  if (threadIdx.x == 0) offsets[K] = total;
 }
 
 __global__ __launch_bounds__(PT_T) void partition_scatter_kernel(const int32_t* __restrict__ labels, int64_t n, int K,
@@ -205,9 +186,10 @@ hipError_t launch_ivf_pack(const IvfPackArgs& a, hipStream_t s) {
   if (a.nb <= 0) return hipSuccess;
   if (a.D > a.dpad || a.K < 1) return hipErrorInvalidValue;
   const unsigned nb = (unsigned)((a.nb + 31) / 32);
-  if (a.dtype == DT_BF16) hipLaunchKernelGGL(ivf_pack_kernel<uint16_t>, dim3(nb), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(ivf_pack_kernel<float>, dim3(nb), dim3(256), 0, s, a);
-  return hipGetLastError();
+  return (hipError_t)for_type(a.dtype, [&](auto t) {
+    hipLaunchKernelGGL(ivf_pack_kernel<typename decltype(t)::type>, dim3(nb), dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 // ---- 2b. repack ----------------------------------------------------------------------------
@@ -260,7 +242,7 @@ __global__ __launch_bounds__(RP_NW * 64) void ivf_repack_kernel(IvfRepackArgs a,
 hipError_t launch_ivf_repack(const IvfRepackArgs& a, hipStream_t s) {
   if (a.n <= 0 || a.n_old <= 0 || a.rows_new <= 0 || a.rows_old <= 0) return hipSuccess;
   if (a.D > a.dpad || a.K < 1) return hipErrorInvalidValue;
-  const int piece = a.dtype == DT_BF16 ? 8 : 4;   // elements of a 16-byte piece
+  const int piece = dtype_vec(a.dtype);
   if (a.dpad % (4 * piece) != 0 || a.rows_new % 16 != 0 || a.rows_old % 16 != 0) return hipErrorInvalidValue;
   const int64_t nb = (a.rows_new / 16 + RP_NW - 1) / RP_NW;
   if (nb > 0x7fffffff) return hipErrorInvalidValue;
@@ -349,7 +331,7 @@ static hipError_t launch_is(int P, int64_t nb, const IvfScanArgs& a, hipStream_t
 
 // Pair blocks per wave: topk's rule (topk_blocks, then walk_blocks over the pairs)
 int ivf_scan_blocks(int dtype, int dpad, int m, int64_t npairs) {
-  const int nq = dpad / 4 / (dtype == DT_BF16 ? 8 : 4);
+  const int nq = dpad / 4 / dtype_vec(dtype);
   return walk_blocks(topk_blocks(nq, m <= 8 ? 8 : 32), npairs);
 }
 

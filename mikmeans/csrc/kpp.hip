@@ -2,7 +2,8 @@
 //
 // k-means++ (Arthur & Vassilvitskii 2007) is K-1 dependent passes.  Each pass:
 //   K5 kpp_d2     d2[i] = min(d2[i], |x_i - c_new|^2) over fixed row blocks, plus an
-//                 f64 partial sum per block (memory-bound streaming pass).
+//                 f64 partial sum per block (memory-bound streaming pass): each thread's rows
+//                 in order, then block.h's wave sums added in wave order.
 //   K6 kpp_sample one workgroup turns u*sum(d2) into an index with two
 //                 prefix-sum searches (blocks, then rows) and copies the chosen
 //                 row into C[k].  No host synchronisation anywhere, so all K-1
@@ -16,7 +17,7 @@
 // the dataset is identical for any world size.
 #include <stdlib.h>
 
-#include "common.h"
+#include "block.h"
 #include "kernels.h"
 
 namespace mk {
@@ -162,33 +163,9 @@ __global__ __launch_bounds__(KPP_NT) void kpp_d2_kernel(const T* __restrict__ X,
       }
     }
   }
-  part = wave_sum(part);
   __shared__ double red[KPP_NT / 64];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = part;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0;
-    for (int w = 0; w < KPP_NT / 64; ++w) s += red[w];
-    block_sums[blockIdx.x] = s;
-  }
-}
-
-template <typename T, bool PRUNE>
-static void launch_kpp_d2_t(const void* X, int64_t N, int D, int64_t ldx, const float* c, int first,
-                            float* d2, double* block_sums, int64_t rows_per_block, int nblocks,
-                            size_t lds, int32_t* owner, const float* cc, int kcc, int knew,
-                            hipStream_t s) {
-  const int pieces = (D * (int)sizeof(T) + 15) / 16;  // 16-byte pieces per row
-  const T* Xt = (const T*)X;
-#define MK_KPP_LAUNCH(L)                                                                         \
-  hipLaunchKernelGGL((kpp_d2_kernel<T, L, PRUNE>), dim3(nblocks), dim3(KPP_NT), lds, s, Xt, N, D, \
-                     ldx, c, first, d2, block_sums, rows_per_block, owner, cc, kcc, knew)
-  if (pieces >= 16) MK_KPP_LAUNCH(16);
-  else if (pieces >= 8) MK_KPP_LAUNCH(8);
-  else if (pieces >= 4) MK_KPP_LAUNCH(4);
-  else if (pieces >= 2) MK_KPP_LAUNCH(2);
-  else MK_KPP_LAUNCH(1);
-#undef MK_KPP_LAUNCH
+  block_wave_sums<KPP_NT>(part, red);
+  if (threadIdx.x == 0) block_sums[blockIdx.x] = sum_in_order(red, KPP_NT / 64);
 }
 
 hipError_t launch_kpp_d2(int dtype, const void* X, int64_t N, int D, int64_t ldx, const float* c,
@@ -199,22 +176,21 @@ hipError_t launch_kpp_d2(int dtype, const void* X, int64_t N, int D, int64_t ldx
   if (D < 1 || D > KPP_MAX_D) return hipErrorInvalidValue;
   size_t lds = (size_t)kpp_cs_floats(D) * 4;
   if (prune && kpp_cc_in_lds(D, kcc)) lds += (size_t)kcc * 4;
-  if (dtype == DT_BF16) {
-    if (prune)
-      launch_kpp_d2_t<uint16_t, true>(X, N, D, ldx, c, 0, d2, block_sums, rows_per_block, nblocks, lds,
-                                      owner, cc, kcc, knew, s);
-    else
-      launch_kpp_d2_t<uint16_t, false>(X, N, D, ldx, c, first, d2, block_sums, rows_per_block, nblocks,
-                                       lds, nullptr, nullptr, 0, -1, s);
-  } else {
-    if (prune)
-      launch_kpp_d2_t<float, true>(X, N, D, ldx, c, 0, d2, block_sums, rows_per_block, nblocks, lds,
-                                   owner, cc, kcc, knew, s);
-    else
-      launch_kpp_d2_t<float, false>(X, N, D, ldx, c, first, d2, block_sums, rows_per_block, nblocks,
-                                    lds, nullptr, nullptr, 0, -1, s);
-  }
-  return hipGetLastError();
+  if (!prune) { owner = nullptr; cc = nullptr; kcc = 0; knew = -1; }   // (the unpruned pass reads none of them)
+  return (hipError_t)for_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    // lanes per row: the row's 16-byte pieces rounded DOWN to a power of two, on purpose (every
+    // lane of a row group has a piece in the first pass over the row); the other row kernels round up
+    const int lpr = plan::pow2_at_most((D * (int)sizeof(T) + 15) / 16, 16);
+    return for_flag(prune, [&](auto p) {
+      return for_value<1, 2, 4, 8, 16>(lpr, [&](auto l) {
+        hipLaunchKernelGGL((kpp_d2_kernel<T, decltype(l)::value, decltype(p)::value>), dim3(nblocks), dim3(KPP_NT),
+                           lds, s, (const T*)X, N, D, ldx, c, first, d2, block_sums, rows_per_block, owner, cc, kcc,
+                           knew);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 // cc[j] = |cnew - C[j]|^2 for the k centres already chosen (one wave per centre): the
@@ -242,7 +218,9 @@ hipError_t launch_kpp_cc(const float* C, int64_t ldc, int k, int D, const float*
   return hipGetLastError();
 }
 
-// Block-wide inclusive scan (1024 threads) of one double per thread.
+// Block-wide inclusive scan (1024 threads) of one double per thread.  Not block.h's scan: this
+// Hillis-Steele adds across wave boundaries at every step, another f64 association, and moving it
+// could move a k-means++ draw at a rounding boundary.
 __device__ double block_scan_incl(double v, double* sh) {
   const int t = threadIdx.x;
   sh[t] = v;
@@ -386,15 +364,12 @@ hipError_t launch_kpp_sample(int dtype, const double* block_sums, int nblocks, c
                              int64_t N, int64_t rows_per_block, const double* target, const void* X,
                              int D, int64_t ldx, float* crow, int64_t* idx_out, int mode,
                              const double* totals_all, int world, int rank, hipStream_t s) {
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(kpp_sample_kernel<uint16_t>, dim3(1), dim3(1024), 0, s, block_sums, nblocks,
-                       d2, N, rows_per_block, target, (const uint16_t*)X, D, ldx, crow, idx_out,
-                       mode, totals_all, world, rank);
-  else
-    hipLaunchKernelGGL(kpp_sample_kernel<float>, dim3(1), dim3(1024), 0, s, block_sums, nblocks,
-                       d2, N, rows_per_block, target, (const float*)X, D, ldx, crow, idx_out,
-                       mode, totals_all, world, rank);
-  return hipGetLastError();
+  return (hipError_t)for_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(kpp_sample_kernel<T>, dim3(1), dim3(1024), 0, s, block_sums, nblocks, d2, N, rows_per_block,
+                       target, (const T*)X, D, ldx, crow, idx_out, mode, totals_all, world, rank);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -403,7 +378,8 @@ hipError_t launch_kpp_sample(int dtype, const double* block_sums, int nblocks, c
 // w (f64), K draws u (f64).  Step k is two launches, with no host read in between:
 //   wkpp_d2    d2[i] = min(d2[i], |c_i - c_j|^2) against the previous pick j (f64 sums of the
 //              exact f64 differences), then p_i = w_i d2[i] scanned inside each 256-candidate
-//              block (cum[i]: the block's inclusive prefix, part[b]: its total);
+//              block by block.h's block_incl_scan (cum[i]: the block's inclusive prefix,
+//              part[b]: its total);
 //   wkpp_pick  one workgroup: the block prefixes P_b (a chunked scan of part), the target
 //              t = u[k] * total, the first block with P_b + part[b] > t and in it the first
 //              candidate with P_b + cum[i] > t (torch.searchsorted(..., right=True) on the
@@ -411,29 +387,6 @@ hipError_t launch_kpp_sample(int dtype, const double* block_sums, int nblocks, c
 // Every sum has a fixed order, so every rank draws the same centres from the same inputs.
 // Step 0 (state j = -1) draws by weight alone; d2 starts at +inf.
 constexpr int WK_NT = 256;
-
-__device__ __forceinline__ double wave_incl_scan(double v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// Inclusive scan over the 256 threads of a block (4 waves), fixed order; returns the thread's
-// prefix and (all threads) the block total.
-__device__ __forceinline__ double block_incl_scan(double v, double* red, double& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  v = wave_incl_scan(v, lane);
-  if (lane == 63) red[wv] = v;
-  __syncthreads();
-  double off = 0.0;
-  for (int q = 0; q < wv; ++q) off += red[q];
-  total = red[0] + red[1] + red[2] + red[3];
-  __syncthreads();   // (red is reused by the caller's next scan)
-  return v + off;
-}
 
 __global__ __launch_bounds__(WK_NT) void wkpp_d2_kernel(const float* __restrict__ Ct, int64_t M, int D,
                                                        const double* __restrict__ w, double* __restrict__ d2,
@@ -462,7 +415,7 @@ __global__ __launch_bounds__(WK_NT) void wkpp_d2_kernel(const float* __restrict_
     p = j >= 0 ? w[i] * dd : w[i];   // (step 0: by weight alone)
   }
   double total;
-  const double c = block_incl_scan(p, red, total);
+  const double c = block_incl_scan<WK_NT>(p, red, total);
   if (i < M) cum[i] = c;
   if (threadIdx.x == 0) part[blockIdx.x] = total;
 }
@@ -486,7 +439,7 @@ __global__ __launch_bounds__(WK_NT) void wkpp_pick_kernel(const float* __restric
       const int b = b0 + (int)threadIdx.x;
       const double prev = (b < nb && threadIdx.x > 0) ? part[b - 1] : 0.0;
       double tot;
-      const double excl = block_incl_scan(prev, red, tot) + carry;
+      const double excl = block_incl_scan<WK_NT>(prev, red, tot) + carry;
       const double own = b < nb ? part[b] : 0.0;
       const int last = b0 + WK_NT - 1 < nb ? b0 + WK_NT - 1 : nb - 1;
       if (b == last) sh_carry = excl + own;   // (one writer: the chunk's last block)
@@ -712,46 +665,33 @@ hipError_t launch_blobs(int dtype, void* X, int64_t i0, int64_t n, int D, int64_
                         const float* centers, int n_centers, float stddev, uint64_t seed,
                         int32_t* y, float* xn, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  const int el = dtype == DT_BF16 ? 8 : 4;  // values per group (see blobs_kernel)
+  const int el = dtype_vec(dtype);  // values per group (see blobs_kernel)
   const int G = (D + el - 1) / el;
   const int es = dtype == DT_BF16 ? 2 : 4;
   const int vec = ((uintptr_t)X % 16 == 0 && (ldx * es) % 16 == 0 && D % el == 0 &&
                    (uintptr_t)centers % 16 == 0) ? 1 : 0;
-  int tpr = 1;
   // Lanes per row: the row's blob-id Philox runs once per wave whatever the number of
   // active lanes, so fewer lanes per row (more rows per wave) amortise it over more
   // groups (8 lanes x 16 B still store whole 128-B lines; profiles/r1_18_blobs_tpr_ab.json:
   // 2.91 -> 2.69 ms per 16.8M x 256 bf16 batch).  Variant V_BLOBS_TPR (1..16) overrides the
   // cap for A/B runs.  The rows do not depend on it; the fused norms' f32 summation order does.
   const int tv = variant(V_BLOBS_TPR);
-  const int tpr_cap = tv < 0 ? 8 : (tv >= 1 && tv <= 16 ? tv : 16);
-  while (tpr < G && tpr * 2 <= tpr_cap) tpr *= 2;
+  const int tpr = plan::pow2_at_least(G, tv < 0 ? 8 : (tv >= 1 && tv <= 16 ? tv : 16));
   // 256 rows per workgroup step; at most 16 workgroups per CU's worth of grid (then strided)
   int64_t nb64 = (n + 255) / 256;
   if (nb64 > 4096) nb64 = 4096;
   const unsigned nb = (unsigned)nb64;
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#define MK_BLOBS(TT, TP)                                                                           \
-  do {                                                                                             \
-    if (xn)                                                                                        \
-      hipLaunchKernelGGL((blobs_kernel<TT, TP, true>), dim3(nb), dim3(256), 0, s, (TT*)X, i0, n, D, \
-                         ldx, centers, n_centers, stddev, k0, k1, y, xn, vec);                     \
-    else                                                                                           \
-      hipLaunchKernelGGL((blobs_kernel<TT, TP, false>), dim3(nb), dim3(256), 0, s, (TT*)X, i0, n,  \
-                         D, ldx, centers, n_centers, stddev, k0, k1, y, xn, vec);                  \
-  } while (0)
-#define MK_BLOBS_T(TT)                                                                           \
-  switch (tpr) {                                                                                 \
-    case 1: MK_BLOBS(TT, 1); break;                                                              \
-    case 2: MK_BLOBS(TT, 2); break;                                                              \
-    case 4: MK_BLOBS(TT, 4); break;                                                              \
-    case 8: MK_BLOBS(TT, 8); break;                                                              \
-    default: MK_BLOBS(TT, 16); break;                                                            \
-  }
-  if (dtype == DT_BF16) { MK_BLOBS_T(uint16_t) } else { MK_BLOBS_T(float) }
-#undef MK_BLOBS_T
-#undef MK_BLOBS
-  return hipGetLastError();
+  return (hipError_t)for_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return for_flag(xn != nullptr, [&](auto norms) {
+      return for_value<1, 2, 4, 8, 16>(tpr, [&](auto l) {
+        hipLaunchKernelGGL((blobs_kernel<T, decltype(l)::value, decltype(norms)::value>), dim3(nb), dim3(256), 0, s,
+                           (T*)X, i0, n, D, ldx, centers, n_centers, stddev, k0, k1, y, xn, vec);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
 }  // namespace mk

@@ -21,6 +21,19 @@
 namespace mk {
 namespace plan {
 
+// The lanes-per-row rules of the row kernels: the smallest power of two >= n and the largest <= n,
+// both at least 1 and at most cap (a cap that is no power of two rounds down).
+constexpr int pow2_at_least(int n, int cap) {
+  int x = 1;
+  while (x < n && x <= cap / 2) x *= 2;
+  return x;
+}
+constexpr int pow2_at_most(int n, int cap) {
+  int x = 1;
+  while (x <= n / 2 && x <= cap / 2) x *= 2;
+  return x;
+}
+
 constexpr size_t UPD_LDS_MAX = 160 * 1024;  // one LDS-filling M-step workgroup per CU
 constexpr int FX_BITS = 20;                 // |q| <= 2^20 per fixed-point contribution
 

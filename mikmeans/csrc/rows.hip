@@ -14,7 +14,7 @@
 // Reference parity: the reference's "Shuffle unassigned" (app.mjs:159-166, Fisher-Yates
 // over the cards) is its only random selection of points; mini-batch sampling is the
 // numeric framework's use of it.
-#include "common.h"
+#include "block.h"    // the workgroup scan and the fixed-order sums of wdot and the compaction
 #include "kernels.h"
 
 namespace mk {
@@ -24,9 +24,7 @@ constexpr uint32_t TAG_SMP = 0x53414D50u;  // "SAMP"
 __device__ __forceinline__ int64_t sample_index(int64_t j, uint32_t step, uint32_t rank, int64_t n,
                                                 uint32_t k0, uint32_t k1) {
   const U4 r = philox(U4{(uint32_t)j, step, rank, TAG_SMP}, k0, k1);
-  const uint64_t w = ((uint64_t)r.y << 32) | r.x;
-  const double u = (double)(w >> 11) * 0x1p-53;
-  const int64_t i = (int64_t)(u * (double)n);
+  const int64_t i = (int64_t)(philox_u53(r) * (double)n);
   return i < n ? i : n - 1;
 }
 
@@ -54,10 +52,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const T* __restrict__ 
     T* op = out + j * ldo;
     for (int p = t; p < NP; p += TPR) {
       const u32x4 w = *(const u32x4*)(rp + p * V);
-      float f[V];
-      unpack16(w, f, (T*)nullptr);
-#pragma unroll
-      for (int q = 0; q < V; ++q) sq = __builtin_fmaf(f[q], f[q], sq);
+      sq = piece_sqnorm<T>(w, sq);
       *(u32x4*)(op + p * V) = w;
     }
   }
@@ -73,29 +68,21 @@ hipError_t launch_sample_rows(int dtype, const void* X, int64_t n, int64_t ldx, 
                               float* xn, int64_t* idx_out, hipStream_t s) {
   if (b <= 0) return hipSuccess;
   if (n <= 0) return hipErrorInvalidValue;
-  const int V = dtype == DT_BF16 ? 8 : 4;
+  const int V = dtype_vec(dtype);
   if (D % V) return hipErrorInvalidValue;
   const int NP = D / V;
-  int tpr = 1;
-  while (tpr < NP && tpr < 16) tpr *= 2;
+  const int tpr = plan::pow2_at_least(NP, 16);
   const int64_t tot = b * tpr;
   const dim3 g((unsigned)((tot + 255) / 256)), blk(256);
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#define MK_SMP(TT, TP)                                                                           \
-  hipLaunchKernelGGL((sample_rows_kernel<TT, TP>), g, blk, 0, s, (const TT*)X, n, ldx, NP, (TT*)out, \
-                     ldo, b, k0, k1, rank, step, xn, idx_out)
-#define MK_SMP_T(TT)                                                                             \
-  switch (tpr) {                                                                                 \
-    case 1: MK_SMP(TT, 1); break;                                                                \
-    case 2: MK_SMP(TT, 2); break;                                                                \
-    case 4: MK_SMP(TT, 4); break;                                                                \
-    case 8: MK_SMP(TT, 8); break;                                                                \
-    default: MK_SMP(TT, 16); break;                                                              \
-  }
-  if (dtype == DT_BF16) { MK_SMP_T(uint16_t) } else { MK_SMP_T(float) }
-#undef MK_SMP_T
-#undef MK_SMP
-  return hipGetLastError();
+  return (hipError_t)for_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return for_value<1, 2, 4, 8, 16>(tpr, [&](auto l) {
+      hipLaunchKernelGGL((sample_rows_kernel<T, decltype(l)::value>), g, blk, 0, s, (const T*)X, n, ldx, NP,
+                         (T*)out, ldo, b, k0, k1, rank, step, xn, idx_out);
+      return hipGetLastError();
+    });
+  });
 }
 
 __global__ __launch_bounds__(256) void sample_index_kernel(int64_t n, int64_t b, uint32_t k0, uint32_t k1,
@@ -126,12 +113,7 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(T* X, int64_t N, int
   T* row = X + (ok ? i : 0) * ldx;
   float s = 0.f;
   if (ok)
-    for (int p = sub; p < NP; p += 16) {
-      float f[V];
-      unpack16(*(const u32x4*)(row + p * V), f, (T*)nullptr);
-#pragma unroll
-      for (int q = 0; q < V; ++q) s = __builtin_fmaf(f[q], f[q], s);
-    }
+    for (int p = sub; p < NP; p += 16) s = piece_sqnorm<T>(*(const u32x4*)(row + p * V), s);
   s = sum16_xor(s);
   const float nrm = fmaxf(sqrtf(s), 1e-30f);
   float s2 = 0.f;
@@ -156,21 +138,22 @@ __global__ __launch_bounds__(256) void row_normalize_kernel(T* X, int64_t N, int
 
 hipError_t launch_row_normalize(int dtype, void* X, int64_t N, int D, int64_t ldx, float* xn, hipStream_t s) {
   if (N <= 0) return hipSuccess;
-  const int V = dtype == DT_BF16 ? 8 : 4;
+  const int V = dtype_vec(dtype);
   if (D % V) return hipErrorInvalidValue;
   const dim3 g((unsigned)((N + 15) / 16)), b(256);
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(row_normalize_kernel<uint16_t>, g, b, 0, s, (uint16_t*)X, N, D / V, ldx, xn);
-  else
-    hipLaunchKernelGGL(row_normalize_kernel<float>, g, b, 0, s, (float*)X, N, D / V, ldx, xn);
-  return hipGetLastError();
+  return (hipError_t)for_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(row_normalize_kernel<T>, g, b, 0, s, (T*)X, N, D / V, ldx, xn);
+    return hipGetLastError();
+  });
 }
 
 // ---------------------------------------------------------------------------
 // out[0] += sum_i a[i] * b[i] in f64 (weighted inertia: a = squared distances, b = weights).
 // Deterministic: a fixed grid of WDOT_BLOCKS blocks writes per-block partials (each summed
-// in a fixed order), and one block adds them in index order -- the same bits on every run,
-// so a hipGraph replay reproduces the eager step exactly.
+// in a fixed order), and one block adds them in a fixed order -- the same bits on every run,
+// so a hipGraph replay reproduces the eager step exactly.  Both kernels: a per-thread strided
+// f64 sum, then block.h's wave sums (the xor butterfly 32 .. 1) combined (r0 + r1) + (r2 + r3).
 constexpr int WDOT_BLOCKS = 1024;
 
 __global__ __launch_bounds__(256) void wdot_partial_kernel(const float* __restrict__ a, const float* __restrict__ b,
@@ -178,21 +161,17 @@ __global__ __launch_bounds__(256) void wdot_partial_kernel(const float* __restri
   double acc = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
     acc += (double)a[i] * (double)b[i];
-  acc = wave_sum(acc);
   __shared__ double red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  block_wave_sums<256>(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = sum_pairs4(red);
 }
 
 __global__ __launch_bounds__(256) void wdot_final_kernel(const double* __restrict__ part, int nb, double* out) {
   double acc = 0.0;
   for (int i = threadIdx.x; i < nb; i += 256) acc += part[i];
-  acc = wave_sum(acc);
   __shared__ double red[4];
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] += (red[0] + red[1]) + (red[2] + red[3]);
+  block_wave_sums<256>(acc, red);
+  if (threadIdx.x == 0) out[0] += sum_pairs4(red);
 }
 
 int wdot_scratch_len() { return WDOT_BLOCKS; }
@@ -434,21 +413,21 @@ hipError_t launch_tighten(int dtype, const void* X, int64_t ldx, int D, const in
   if (n_max <= 0) return hipSuccess;
   int64_t nb = (n_max + 15) / 16;   // 16 rows per block and pass
   if (nb > 8192) nb = 8192;
-  if (dtype == DT_BF16)
-    hipLaunchKernelGGL(tighten_kernel<uint16_t>, dim3((unsigned)nb), dim3(256), 0, s, (const uint16_t*)X, ldx, D,
-                       labels, C, ldc, rows, count, ub, lb, cand, xn, work, oseed, D);
-  else
-    hipLaunchKernelGGL(tighten_kernel<float>, dim3((unsigned)nb), dim3(256), 0, s, (const float*)X, ldx, D, labels,
-                       C, ldc, rows, count, ub, lb, cand, xn, work, oseed, D);
-  return hipGetLastError();
+  return (hipError_t)for_type(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL(tighten_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, (const T*)X, ldx, D, labels, C, ldc,
+                       rows, count, ub, lb, cand, xn, work, oseed, D);
+    return hipGetLastError();
+  });
 }
 
 // ---- candidate compaction ----------------------------------------------------------------
 // rows[0..count) = the indices i with cand[i] != 0, ascending; count stays on the device.
 // Three launches, no atomics (so the order -- and with it each row's workgroup in the
 // gathered assign that follows -- is the same every run): per-block counts of 4096 flags,
-// one workgroup's exclusive scan of those counts, and a write pass whose threads place
-// their 16 flags' rows after the block offset plus an in-block scan.
+// one workgroup's exclusive scan of those counts (block.h scan_slices), and a write pass whose
+// threads place their 16 flags' rows after the block offset plus an in-block scan (block.h
+// block_incl_scan).
 constexpr int CMP_T = 256, CMP_R = 16, CMP_ROWS = CMP_T * CMP_R;
 
 __device__ __forceinline__ int flags16(const uint8_t* __restrict__ cand, int64_t base, int64_t n, unsigned& bits) {
@@ -470,52 +449,17 @@ __device__ __forceinline__ int flags16(const uint8_t* __restrict__ cand, int64_t
 __global__ __launch_bounds__(CMP_T) void compact_count_kernel(const uint8_t* __restrict__ cand, int64_t n,
                                                            int64_t* __restrict__ bcnt) {
   unsigned bits;
-  int c = flags16(cand, (int64_t)blockIdx.x * CMP_ROWS + threadIdx.x * CMP_R, n, bits);
-  c = wave_sum(c);
+  const int c = flags16(cand, (int64_t)blockIdx.x * CMP_ROWS + threadIdx.x * CMP_R, n, bits);
   __shared__ int ws[CMP_T / 64];
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < CMP_T / 64; ++w) t += ws[w];
-    bcnt[blockIdx.x] = t;
-  }
-}
-
-// inclusive scan of one value per thread over a workgroup of T threads (T / 64 waves)
-template <int T>
-__device__ __forceinline__ int64_t block_incl_scan(int64_t v, int64_t* lds_waves) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) lds_waves[w] = v;
-  __syncthreads();
-  int64_t before = 0;
-  for (int j = 0; j < w; ++j) before += lds_waves[j];
-  __syncthreads();   // (lds_waves is reused by the caller's next scan)
-  return v + before;
+  block_wave_sums<CMP_T>(c, ws);
+  if (threadIdx.x == 0) bcnt[blockIdx.x] = sum_in_order(ws, CMP_T / 64);
 }
 
 __global__ __launch_bounds__(1024) void compact_scan_kernel(int64_t* __restrict__ bcnt, int64_t nb,
                                                          int64_t* __restrict__ count) {
-  __shared__ int64_t wsum[16];
-  __shared__ int64_t tot;
-  int64_t carry = 0;
-  for (int64_t s0 = 0; s0 < nb; s0 += 1024) {
-    const int64_t i = s0 + threadIdx.x;
-    const int64_t v = i < nb ? bcnt[i] : 0;
-    const int64_t incl = block_incl_scan<1024>(v, wsum);
-    if (i < nb) bcnt[i] = carry + incl - v;   // exclusive offset
-    if (threadIdx.x == 1023) tot = incl;      // this slice's total
-    __syncthreads();
-    carry += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) count[0] = carry;
+  const int64_t total = scan_slices<1024>(
+      nb, [&](int64_t i) { return bcnt[i]; }, [&](int64_t i, int64_t excl) { bcnt[i] = excl; });
+  if (threadIdx.x == 0) count[0] = total;
 }
 
 __global__ __launch_bounds__(CMP_T) void compact_write_kernel(const uint8_t* __restrict__ cand, int64_t n,
@@ -525,7 +469,8 @@ __global__ __launch_bounds__(CMP_T) void compact_write_kernel(const uint8_t* __r
   const int64_t base = (int64_t)blockIdx.x * CMP_ROWS + threadIdx.x * CMP_R;
   unsigned bits;
   const int c = flags16(cand, base, n, bits);
-  const int64_t incl = block_incl_scan<CMP_T>((int64_t)c, wsum);
+  int64_t total;   // (unused: the block offsets come from the scan kernel)
+  const int64_t incl = block_incl_scan<CMP_T>((int64_t)c, wsum, total);
   int64_t pos = boff[blockIdx.x] + incl - c;
   while (bits) {
     const int j = __builtin_ctz(bits);
@@ -563,8 +508,7 @@ __global__ __launch_bounds__(256) void kpar_select_kernel(const float* __restric
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const uint64_t g = (uint64_t)(start + i);
     const U4 r = philox(U4{(uint32_t)g, (uint32_t)(g >> 32), round, TAG_KPAR}, k0, k1);
-    const uint64_t w = ((uint64_t)r.y << 32) | r.x;
-    const double u = (double)(w >> 11) * 0x1p-53;
+    const double u = philox_u53(r);
     cand[i] = (ps > 0.0 && u < ell * (double)d2[i] / ps) ? 1 : 0;
   }
 }

@@ -10,6 +10,7 @@ inputs in interleaved rounds, so box-to-box clock differences cancel.
 
   python scripts/ab_ext.py build HEAD~1            # prints the module path
   python scripts/ab_ext.py run scripts/abbin/_C_ab_<sha>.so --n 20000000 --d 128 --k 1024
+  python scripts/ab_ext.py run scripts/abbin/_C_ab_<sha>.so --what rows   # the row kernels, bit for bit
 """
 from __future__ import annotations
 
@@ -75,6 +76,204 @@ def _timed(fn, reps):
     return ts
 
 
+def _rows_cases(torch, dev):
+    """The row kernels' cases (csrc/rows.hip, csrc/kpp.hip, the partition of csrc/ivf.hip, the two
+    radix selects): ``(kernel, case, prep)`` with ``prep(m) -> (run, outputs)`` on module ``m``;
+    ``run()`` launches the case from the same input state every time, ``outputs`` are what it
+    wrote.  Inputs come from a seed of the case's own, so every module sees the same."""
+    i32, i64, f32, f64 = torch.int32, torch.int64, torch.float32, torch.float64
+
+    def gen(seed):
+        return torch.Generator(device=dev).manual_seed(seed)
+
+    def new(shape, dtype, fill=0):
+        return torch.full(shape if isinstance(shape, tuple) else (shape,), fill, dtype=dtype, device=dev)
+
+    ns = (1, 65, 4097, 300_001)
+    for dt in (torch.bfloat16, f32):
+        v = 8 if dt == torch.bfloat16 else 4
+        for D in (4, 20, 128, 1024):
+            Dp = -(-D // v) * v
+            for n in ns:
+                tag = f"{'bf16' if dt == torch.bfloat16 else 'f32'} n={n} D={D}"
+                g = gen(n + D)
+                X = torch.zeros((n, Dp), dtype=dt, device=dev)
+                X[:, :D] = (torch.randn((n, D), generator=g, device=dev) * 3).to(dt)
+                X[n // 2] = 0     # (a zero row: the normalise's floor, a zero distance)
+
+                def smp(m, X=X, n=n):
+                    out, xn, idx = torch.empty_like(X), new(n, f32), new(n, i64)
+                    return (lambda: m.sample_rows(X, out, n, 99, 1, 7, xn, idx)), (out, xn, idx)
+
+                def nrm(m, X=X, n=n):
+                    Y, xn = X.clone(), new(n, f32)
+
+                    def run():
+                        Y.copy_(X)
+                        m.row_normalize(Y, xn)
+                    return run, (Y, xn)
+
+                rpb = 1024
+                nb = -(-n // rpb)
+                c3 = [X[(j * 7919) % n].float().contiguous() for j in range(3)]
+
+                def kd2(m, X=X, n=n, nb=nb, c3=c3):   # the first pass, two pruned passes, one unpruned
+                    d2, d2u, own = new(n, f32), new(n, f32), new(n, i32)
+                    bs = [new(nb, f64) for _ in range(4)]
+                    cc = [new(3, f32), new(3, f32)]   # (one slot a centre, as the seeding holds them)
+                    C = torch.stack(c3)
+
+                    def run():
+                        own.zero_()
+                        m.kpp_d2(X, c3[0], True, d2, bs[0], rpb)
+                        d2u.copy_(d2)
+                        m.kpp_d2(X, c3[1], False, d2u, bs[3], rpb)
+                        m.kpp_cc(C, 1, c3[1], cc[0])
+                        m.kpp_d2(X, c3[1], False, d2, bs[1], rpb, own, cc[0], 1, 1)
+                        m.kpp_cc(C, 2, c3[2], cc[1])
+                        m.kpp_d2(X, c3[2], False, d2, bs[2], rpb, own, cc[1], 2, 2)
+                    return run, (d2, d2u, own, *bs, *cc)
+
+                def ksm(m, X=X, n=n, nb=nb):
+                    d2 = torch.rand(n, generator=gen(n), device=dev) ** 4
+                    d2[::3] = 0
+                    pad = torch.zeros(nb * rpb, dtype=f64, device=dev)
+                    pad[:n] = d2.double()
+                    bsum = pad.view(nb, rpb).sum(1)
+                    crow, idx = new(X.shape[1], f32), new(1, i64)
+                    tgt = torch.tensor([0.37], dtype=f64, device=dev)
+                    return (lambda: m.kpp_sample(bsum, d2, rpb, tgt, X, crow, idx, 1, None, 0)), (crow, idx)
+
+                yield "sample_rows", tag, smp
+                yield "row_normalize", tag, nrm
+                yield "kpp_d2 + kpp_cc", tag, kd2
+                yield "kpp_sample", tag, ksm
+                del X
+    for n in ns + (4_198_401,):
+        g = gen(n)
+        if n <= ns[-1]:
+            a_, w_ = torch.randn(n, generator=g, device=dev) * 3, torch.randn(n, generator=g, device=dev)
+
+            def wd(m, a_=a_, w_=w_):
+                out, scr = new(1, f64), new(m.WDOT_SCRATCH, f64)
+
+                def run():
+                    out.fill_(0.37)
+                    m.wdot(a_, w_, out, scr)
+                return run, (out, scr)
+
+            d2 = torch.rand(n, generator=g, device=dev) ** 4 * 50
+            psi = d2.double().sum().reshape(1)
+
+            def kps(m, d2=d2, psi=psi, n=n):
+                cand = new(n, torch.uint8)
+                return (lambda: m.kpar_select(d2, (1 << 32) - 5, psi, 2000.0, 11, 3, cand)), (cand,)
+
+            yield "wdot", f"n={n}", wd
+            yield "kpar_select", f"n={n}", kps
+        flags = (torch.rand(n, generator=g, device=dev) < 0.3).to(torch.uint8)
+
+        def cmp_(m, flags=flags, n=n):
+            rows, cnt, scr = new(n, i64, -7), new(1, i64, -1), new(max(1, m.compact_blocks(n)), i64)
+            return (lambda: m.compact(flags, rows, cnt, scr)), (rows, cnt, scr)
+
+        yield "compact", f"n={n}", cmp_
+    for M in (257, 70_000):
+        g = gen(M)
+        Ct = torch.randn((8, M), generator=g, device=dev)
+        w = torch.randint(0, 20, (M,), generator=g, device=dev).double()
+        u = torch.rand(3, generator=g, dtype=f64, device=dev)
+
+        def wk(m, Ct=Ct, w=w, u=u, M=M):
+            d2, cum, part = new(M, f64), new(M, f64), new(-(-M // 256), f64)
+            state, out, init = new(2, i64), new((3, 8), f32), torch.tensor([-1, 0], device=dev)
+
+            def run():
+                d2.fill_(float("inf"))
+                state.copy_(init)
+                m.wkpp(Ct, w, d2, cum, part, u, state, out, 3)
+            return run, (cum, part, out, state, d2)
+
+        yield "wkpp", f"M={M}", wk
+    for n, K in [(n, 37) for n in ns] + [(70_001, 1024)]:
+        lab = torch.randint(-1, K + 1, (n,), generator=gen(n + K), device=dev).to(i32)
+
+        def pt(m, lab=lab, n=n, K=K):
+            order, offs, rpos = new(n, i64), new(K + 1, i64), new(n, i64)
+            cells = new(K * m.partition_blocks(n, K), i64)
+            return (lambda: m.partition(lab, K, order, offs, cells, rpos)), (order, offs, cells, rpos)
+
+        yield "partition", f"n={n} K={K}", pt
+    for K in ns[:3]:
+        g = gen(K)
+        t0 = torch.randint(0, 1000, (K, 256), generator=g, device=dev) * (torch.rand((K, 1), generator=g, device=dev) > 0.2)
+        t1 = torch.randint(0, 1000, (K, 3, 256), generator=g, device=dev)
+        q = torch.tensor([0.1, 0.5, 0.99], dtype=f64, device=dev)
+
+        def qs(m, t0=t0, t1=t1, K=K):
+            pre, rank, cnt = new((K, 3), i32), new((K, 3), i64), new(K, i64)
+            p0, r0 = new((K, 3), i32), new((K, 3), i64)
+
+            def run():
+                m.quantile_select(t0, q, pre, rank, cnt, 0)
+                p0.copy_(pre)
+                r0.copy_(rank)
+                m.quantile_select(t1, q, pre, rank, cnt, 1)
+            return run, (pre, rank, cnt, p0, r0)
+
+        s0 = torch.randint(0, 50, (K, 256), generator=g, device=dev).to(i32)
+        s1 = torch.randint(0, 50, (K, 256), generator=g, device=dev).to(i32)
+
+        def isel(m, s0=s0, s1=s1, K=K):
+            pre, st = new(K, i32), [new(K, i64) for _ in range(3)]
+            first = [new(K, i32)] + [new(K, i64) for _ in range(3)]
+
+            def run():
+                m.ivf_select(s0, pre, *st, 100, 0)
+                for d, s in zip(first, [pre, *st]):
+                    d.copy_(s)
+                m.ivf_select(s1, pre, *st, 100, 1)
+            return run, (pre, *st, *first)
+
+        yield "quantile_select", f"K={K}", qs
+        yield "ivf_select", f"nq={K}", isel
+
+
+def cmd_rows(mods, a) -> int:
+    """``--what rows``: every case on every module, outputs compared bit for bit with the head's
+    (floats as integer views) and timed in interleaved rounds; one JSON line, a kernel a key."""
+    import torch
+
+    dev = torch.device("cuda")
+    ints = {torch.float32: torch.int32, torch.float64: torch.int64, torch.bfloat16: torch.int16}
+    res = {}
+    for kernel, case, prep in _rows_cases(torch, dev):
+        k = res.setdefault(kernel, {"cases": 0, "differ": [], "rounds": {t: [0.0] * a.rounds for t in mods}})
+        k["cases"] += 1
+        runs, snap = {}, {}
+        for tag, m in mods.items():
+            runs[tag], outs = prep(m)
+            runs[tag]()          # (also the warm-up)
+            torch.cuda.synchronize()
+            snap[tag] = [o.view(ints.get(o.dtype, o.dtype)).clone() for o in outs]
+        for tag in mods:
+            if not all(torch.equal(x, y) for x, y in zip(snap[tag], snap["head"])):
+                k["differ"].append(f"{tag}: {case}")
+        for r in range(a.rounds):
+            for tag in mods:
+                k["rounds"][tag][r] += statistics.median(_timed(runs[tag], a.reps))
+        del runs, snap
+    out = {"what": "rows", "rounds": a.rounds, "reps": a.reps, "kernels": {}}
+    for kernel, k in res.items():
+        # per round, the sum over the kernel's cases of the round's median; their median and spread
+        out["kernels"][kernel] = {"cases": k["cases"], "outputs_equal_head": not k["differ"], "differ": k["differ"],
+                                  "variants": {tag: {"median_ms": round(statistics.median(v), 4),
+                                                     "round_median_spread_ms": round(max(v) - min(v), 4)}
+                                               for tag, v in k["rounds"].items()}}
+    print(json.dumps(out), flush=True)
+    return 0 if all(k["outputs_equal_head"] for k in out["kernels"].values()) else 1
+
+
 def cmd_run(a) -> int:
     import torch
 
@@ -89,6 +288,8 @@ def cmd_run(a) -> int:
         meta = Path(p).with_suffix(".json")
         tag = json.loads(meta.read_text())["ref"] if meta.exists() else Path(p).stem
         mods[tag] = load_module(p)
+    if a.what == "rows":   # its own shapes, many and small (--n / --d / --k / --dtype do not apply)
+        return cmd_rows(mods, a)
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     dev = torch.device("cuda")
     comm = Comm.local(dev)
@@ -280,7 +481,7 @@ def main(argv=None) -> int:
     r.add_argument("--rounds", type=int, default=5)
     r.add_argument("--reps", type=int, default=5)
     r.add_argument("--what", default="assign", choices=["assign", "update", "blobs", "colstats", "rownorms",
-                                                        "transform", "topk", "ivf_scan", "ivf_range"])
+                                                        "transform", "topk", "ivf_scan", "ivf_range", "rows"])
     r.add_argument("--mode", default="plain", choices=["plain", "weighted", "clamp", "resid", "gather", "delta"],
                    help="update: the pass (each reaches another build of the M-step kernels)")
     r.add_argument("--m", type=int, default=8,

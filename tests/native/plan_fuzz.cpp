@@ -1,6 +1,7 @@
 // Host sanitizer harness for the launch planning of csrc/plan.h (built by
 // tests/test_native_host.py with -fsanitize=address,undefined).  Sweeps K in [1, 2^20],
-// D in [1, 256] and N over 1 .. 2^34, and checks every invariant the kernels rely on;
+// D in [1, 256] and N over 1 .. 2^34, and checks every invariant the kernels rely on, then the
+// lanes-per-row rules (pow2_at_least, pow2_at_most) over n in 1..4096 and every cap in 1..64;
 // prints "ok <cases>" or the first violation.
 #include <stdio.h>
 #include <stdlib.h>
@@ -97,6 +98,32 @@ int main() {
     const int e = fixed_exp(m);
     if (e < -126 || e > 126) return fail("exp edge", 0, e, 0);
   }
+  // the lanes-per-row rules against the loops and the if chain they replaced: the capped round-up
+  // (sample_rows, and blobs with its variant cap, powers of two or not), the uncapped round-up of
+  // the column statistics (called with n <= 64 and cap 64) and kpp_d2's round-down (cap 16)
+  for (int n = 1; n <= 4096; ++n) {
+    for (int cap = 1; cap <= 64; ++cap) {
+      int up = 1;
+      while (up < n && up * 2 <= cap) up *= 2;
+      int down = 1;
+      while (down * 2 <= n && down * 2 <= cap) down *= 2;
+      ++cases;
+      if (pow2_at_least(n, cap) != up) return fail("pow2_at_least", n, cap, pow2_at_least(n, cap));
+      if (pow2_at_most(n, cap) != down) return fail("pow2_at_most", n, cap, pow2_at_most(n, cap));
+    }
+    int tpr = 1;
+    while (tpr < n && tpr < 16) tpr *= 2;
+    if (pow2_at_least(n, 16) != tpr) return fail("sample_rows lanes", n, tpr, pow2_at_least(n, 16));
+    if (n <= 64) {
+      int L = 1;
+      while (L < n) L *= 2;
+      if (pow2_at_least(n, 64) != L) return fail("colstat lanes", n, L, pow2_at_least(n, 64));
+    }
+    const int chain = n >= 16 ? 16 : n >= 8 ? 8 : n >= 4 ? 4 : n >= 2 ? 2 : 1;
+    if (pow2_at_most(n, 16) != chain) return fail("kpp_d2 lanes", n, chain, pow2_at_most(n, 16));
+  }
+  static_assert(pow2_at_least(5, 6) == 4 && pow2_at_most(5, 16) == 4 && pow2_at_least(0, 8) == 1 && pow2_at_most(0, 8) == 1,
+                "constexpr, a cap that is no power of two rounds down, never below 1");
   printf("ok %lld\n", cases);
   return 0;
 }

@@ -197,11 +197,12 @@ def test_kmeans_hamerly_fit(native):
         KMeans(4, algorithm="bogus")
 
 
-@pytest.mark.parametrize("n", [1, 15, 16, 4095, 4097, 1_000_003])
+@pytest.mark.parametrize("n", [1, 15, 16, 4095, 4097, 1_000_003, 4_198_401])
 @pytest.mark.parametrize("density", [0.0, 0.003, 0.5, 1.0])
 def test_compact_matches_nonzero(native, n, density):
     """csrc/rows.hip compaction: the flagged rows in ascending order and their count, both on
-    the device, for ragged sizes (16-flag thread groups, 4096-flag blocks, a multi-slice scan)."""
+    the device, for ragged sizes (16-flag thread groups, 4096-flag blocks, and at 4_198_401 flags
+    1026 blocks: the one-workgroup scan takes a second slice of 1024 and carries into it)."""
     g = torch.Generator(device="cpu").manual_seed(n)
     cand = (torch.rand(n, generator=g) < density).to(torch.uint8).to(DEV)
     rows = torch.full((n,), -7, dtype=torch.int64, device=DEV)

@@ -73,7 +73,8 @@ def test_weighted_kmeanspp_graph_equals_eager(native):
     assert torch.unique(b, dim=0).shape[0] == 300
 
 
-@pytest.mark.parametrize("M,D,K", [(300, 8, 40), (41_000, 64, 512), (5_000, 130, 300), (257, 3, 257)])
+@pytest.mark.parametrize("M,D,K", [(300, 8, 40), (41_000, 64, 512), (5_000, 130, 300), (257, 3, 257),
+                                   (70_000, 8, 24)])   # (274 blocks: the pick's scan takes a second chunk of 256)
 def test_native_weighted_recluster_matches_torch(native, M, D, K):
     """The k-means|| recluster on the framework's kernels (csrc/kpp.hip wkpp: f64 d2 update +
     block scans, one-workgroup pick) draws the same candidates as the PyTorch oracle
@@ -96,3 +97,50 @@ def test_native_weighted_recluster_matches_torch(native, M, D, K):
     agree = (ia == ib).float().mean().item()
     assert agree == 1.0, agree
     assert bool((w[ia] > 0).all())
+
+
+def wkpp_step0_emulated(w):
+    """cum and part of wkpp's step 0 (p = w) in the order csrc/block.h block_incl_scan fixes: inside a
+    wave of 64 the ladder v += v[lane - o] for o = 1, 2, .. 32 where lane >= o, then 0.0 plus the sums
+    of the block's earlier waves in wave order; part = the four wave sums added in wave order."""
+    M = w.size
+    nb = -(-M // 256)
+    v = np.zeros(nb * 256)
+    v[:M] = w
+    v = v.reshape(nb, 4, 64)
+    lane = np.arange(64)
+    for o in (1, 2, 4, 8, 16, 32):
+        v = np.where(lane >= o, v + np.roll(v, o, axis=-1), v)
+    red = v[..., 63]
+    prefix = np.zeros((nb, 4))
+    for q in range(1, 4):
+        prefix[:, q] = prefix[:, q - 1] + red[:, q - 1]
+    part = ((red[:, 0] + red[:, 1]) + red[:, 2]) + red[:, 3]
+    return (v + prefix[..., None]).reshape(-1)[:M], part
+
+
+def check_wkpp_step0_order(C_, M):
+    g = torch.Generator().manual_seed(M)
+    w = torch.rand(M, generator=g, dtype=torch.float64)
+    w[torch.rand(M, generator=g) < 0.2] = 0.0
+    D = 3
+    Ct = torch.randn(D, M, generator=g).to(DEV)
+    d2 = torch.full((M,), float("inf"), dtype=torch.float64, device=DEV)
+    cum = torch.full((M,), -1.0, dtype=torch.float64, device=DEV)
+    part = torch.full((-(-M // 256),), -1.0, dtype=torch.float64, device=DEV)
+    state = torch.tensor([-1, 0], dtype=torch.int64, device=DEV)
+    out = torch.empty((1, D), dtype=torch.float32, device=DEV)
+    u = torch.tensor([0.5], dtype=torch.float64, device=DEV)
+    C_.wkpp(Ct, w.to(DEV), d2, cum, part, u, state, out, 1)
+    ecum, epart = wkpp_step0_emulated(w.numpy())
+    assert np.array_equal(cum.cpu().numpy().view(np.int64), ecum.view(np.int64))
+    assert np.array_equal(part.cpu().numpy().view(np.int64), epart.view(np.int64))
+    assert int(state[1]) == 1 and w[int(state[0])] > 0
+
+
+@pytest.mark.parametrize("M", [1, 64, 65, 257, 70_000])
+def test_wkpp_step0_scan_order_is_pinned(native, M):
+    """Step 0 of the recluster (state j = -1, p = w): cum and part are bit for bit the NumPy
+    emulation of the scan order written in csrc/block.h -- the shuffle-up ladder inside a wave, the
+    earlier waves' sums in wave order -- for random f64 weights, some of them zero."""
+    check_wkpp_step0_order(native, M)

@@ -57,6 +57,52 @@ def test_row_normalize_and_wdot(native, dtype):
     assert float(again) == float(out)                  # fixed summation order
 
 
+def _wave_sum(v):
+    """common.h wave_sum over the last axis (64 lanes): v += v[lane ^ o] for o = 32, 16, .. 1; lane 0."""
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., lane ^ o]
+    return v[..., 0]
+
+
+def wdot_emulated(a, w, out0):
+    """out0 + sum a*w in the order csrc/rows.hip's wdot kernels fix (csrc/block.h block_wave_sums,
+    sum_pairs4): min(ceil(n / 256), 1024) blocks of 256 threads, a per-thread strided f64 sum, the xor
+    butterfly inside each wave, the four waves as (r0 + r1) + (r2 + r3); the final kernel the same way
+    over the blocks' partials."""
+    def block_sums(x, nb):   # [nb * 256] threads, each summing x[t], x[t + nb * 256], ... in order
+        T = nb * 256
+        pad = np.zeros(-(-x.size // T) * T)
+        pad[: x.size] = x
+        acc = np.zeros(T)
+        for chunk in pad.reshape(-1, T):
+            acc = acc + chunk
+        r = _wave_sum(acc.reshape(nb, 4, 64))
+        return (r[:, 0] + r[:, 1]) + (r[:, 2] + r[:, 3])
+
+    nb = min(-(-a.size // 256), 1024)
+    part = block_sums(a.astype(np.float64) * w.astype(np.float64), nb)
+    return out0 + block_sums(part, 1)[0]
+
+
+def check_wdot_order(C_, n):
+    g = torch.Generator().manual_seed(n)
+    a, w = torch.randn(n, generator=g) * 3, torch.randn(n, generator=g)
+    out = torch.tensor([0.37], dtype=torch.float64, device=DEV)
+    scratch = torch.empty(C_.WDOT_SCRATCH, dtype=torch.float64, device=DEV)
+    C_.wdot(a.to(DEV), w.to(DEV), out, scratch)
+    exp = np.array([wdot_emulated(a.numpy(), w.numpy(), np.float64(0.37))])
+    assert np.array_equal(out.cpu().numpy().view(np.int64), exp.view(np.int64)), (float(out), float(exp[0]))
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 300_001])
+def test_wdot_sum_order_is_pinned(native, n):
+    """wdot's f64 result is bit for bit the NumPy emulation of the order written at the kernels
+    (strided per-thread sums, xor butterfly 32 .. 1, (r0 + r1) + (r2 + r3), the final kernel the same
+    way), added to a non-zero out."""
+    check_wdot_order(native, n)
+
+
 def test_minibatch_fit_device_vs_host_shard(native, monkeypatch):
     """The same Philox rows on both placements: a device-resident shard (batches drawn by
     the gather kernel) and a host shard over the HBM budget (rows gathered on the host)

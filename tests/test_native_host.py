@@ -56,7 +56,8 @@ def _run_harness(tmp_path, name):
 @pytest.mark.skipif(shutil.which("g++") is None, reason="no host C++ compiler")
 def test_launch_planning_under_asan_ubsan(tmp_path):
     """csrc/plan.h (M-step slice width / LDS bytes / chunks, fixed-point exponent, assign
-    Kpad) swept over K in [1, 2^20], D in [1, 256] under ASan + UBSan (VERDICT r1 #9)."""
+    Kpad) swept over K in [1, 2^20], D in [1, 256] under ASan + UBSan; the
+    lanes-per-row rules pow2_at_least / pow2_at_most against the loops they replaced."""
     _run_harness(tmp_path, "plan_fuzz")
 
 
@@ -64,7 +65,9 @@ def test_launch_planning_under_asan_ubsan(tmp_path):
 def test_width_dispatch_under_asan_ubsan(tmp_path):
     """csrc/dispatch.h for_width, for both element sizes: a case for exactly the widths
     plan::assign_dpad returns over D = 1..1024, every other width in 1..2048 refused; for_value:
-    a case for exactly the values of its list, every other value around it refused uncalled."""
+    a case for exactly the values of its list, every other value around it refused uncalled;
+    for_type: one type tag for every dtype value, bf16 for WIDTH_BF16 alone; for_flag: the flag's
+    constant."""
     _run_harness(tmp_path, "width_fuzz")
 
 
