@@ -47,41 +47,20 @@
 // Layout "16" of the packed centroids (csrc/kernels.h):
 //   element (k, d): t = k/16, r = k%16, q = d / (4V), g = (d / V) % 4
 //   offset = ((t*NQ + q)*64 + r + 16*g)*V + d%V,  NQ = DPAD/(4V)
+//
+// The steps assign16_kernel and assign16_persist_kernel both take -- the ring DMA, the LDS
+// layout, the seed rule, the packed-key tile step, the label decode -- are csrc/assign_step.h.
 #include <cstdlib>
 #include <type_traits>
 
+#include "assign_step.h"   // the steps both kernels take: ring DMA, LDS layout, seed rule, tile step, label decode
 #include "common.h"
 #include "kernels.h"
 #include "plan.h"
-#include "tile.h"   // Mfma16, the k-step (nothing else of it: this kernel streams the centres through LDS)
 
 namespace mk {
 
 using plan::chunk_tiles16;
-
-// CT_: tiles per LDS chunk (0 = the 16 KiB default, which also fixes Kpad's
-// granule); NBUF_: ring slots (prefetch depth NBUF-1).
-template <typename T, int DPAD, int P_, int CT_ = 0, int NBUF_ = 2, int NW_ = 4>
-struct Assign16Cfg {
-  static constexpr int NW = NW_;                // waves per workgroup sharing the ring
-  static constexpr int P = P_;                  // 16-point blocks per wave
-  static constexpr int V = Elem<T>::V;
-  static constexpr int NQ = DPAD / 4 / V;       // 16-B pieces per lane per point
-  static constexpr int TILE_BYTES = NQ * 1024;  // 16 centroids x DPAD
-  static constexpr int CT = CT_ ? CT_ : chunk_tiles16(sizeof(T), DPAD);
-  static constexpr int CHUNK_BYTES = CT * TILE_BYTES;
-  static constexpr int PIECES = CHUNK_BYTES / 1024;
-  static constexpr int NPW = PIECES / NW;
-  static constexpr int PTS = NW * P * 16;
-  static constexpr int PP = (P + 3) / 4 * 4;    // per-point offset slots per lane (LDS, f32x4 reads)
-  static constexpr int OPT_BYTES = 2 * NW * 16 * PP * 4;   // offsets + gathered |x|^2
-  static constexpr int NBUF = NBUF_;
-  static_assert(NBUF == 2 || NBUF == 3, "ring depth");
-  static_assert(chunk_tiles16(sizeof(T), DPAD) % CT == 0 || CT % chunk_tiles16(sizeof(T), DPAD) == 0,
-                "chunk and the Kpad granule must nest (a wider chunk runs only where Kpad is a multiple of it)");
-  static_assert(NQ >= 1, "DPAD too small for the 16x16 layout");
-  static_assert(PIECES % NW == 0, "chunk pieces must split evenly over waves");
-};
 
 // Sum of squares of one lane's 16-byte piece.
 __device__ __forceinline__ float sq16(const u32x4& w, uint16_t*) {
@@ -128,9 +107,9 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
-  const int cn_bytes = ((a.Kpad * 4 + 1023) / 1024) * 1024;
-  char* cn_lds = smem;
-  char* bufs = smem + cn_bytes;
+  const AssignLds<C> L(smem, a.Kpad);
+  const int cn_bytes = L.cn_bytes(a.Kpad);
+  char *cn_lds = L.cn, *bufs = L.ring;
   // Centre split (small N): grid.y splits the chunk range; each split leaves its
   // (value, index) in a.split_keys and split_finish_kernel writes the labels.
   const int nch_all = a.Kpad / (16 * C::CT);
@@ -144,16 +123,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
   const uint32_t loff = (uint32_t)lane * 16u;
   const __amdgpu_buffer_rsrc_t rC = make_rsrc(a.Cpack, (uint32_t)a.Kpad * DPAD * sizeof(T));
   const __amdgpu_buffer_rsrc_t rN = make_rsrc(a.cn, (uint32_t)a.Kpad * 4u);
-  // Ring slots: chunk c sits in slot c % NBUF.
-  auto issue_chunk = [&](int c, int slot) {  // c: chunk index within this split
-    const uint32_t src = (uint32_t)(c0 + c) * C::CHUNK_BYTES;
-    char* dst = bufs + slot * C::CHUNK_BYTES;
-#pragma unroll
-    for (int i = 0; i < C::NPW; ++i) {
-      const int pc = wid + i * C::NW;
-      blds16(rC, (MK_LDS void*)(dst + pc * 1024), loff, src + (uint32_t)pc * 1024u);
-    }
-  };
+  auto issue_chunk = [&](int c, int slot) { ring_issue<C>(rC, bufs, slot, c0 + c, wid, loff); };   // slot c % NBUF
 
   // rows this launch assigns: N, or the device count of a compacted batch (wave-uniform;
   // a workgroup past it leaves before any barrier)
@@ -175,10 +145,9 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
   auto load_frags = [&](int p, int64_t src) {
     const T* rp = (const T*)a.X + src * a.ldx + g * C::V;
 #pragma unroll
-    for (int q = 0; q < C::NQ; ++q) {
-      const int col = (4 * q + g) * C::V;
-      if (FULLD || col < a.D) xr[p][q] = *(const u32x4*)(rp + 4 * q * C::V);
-      else xr[p][q] = u32x4{0u, 0u, 0u, 0u};
+    for (int q = 0; q < C::NQ; ++q) {   // (FULLD: no column compare, see above)
+      if constexpr (FULLD) xr[p][q] = *(const u32x4*)(rp + 4 * q * C::V);
+      else xr[p][q] = load_piece<C::V>(rp, q, g, a.D);
     }
   };
   auto load_block = [&]() {   // fragments (+ caller norms) of the block at pbase
@@ -229,8 +198,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
   // repeat it (harmless to the max / min)
   float xg[EJ];
   if (early) {
-    for (int pc = wid; pc < cn_bytes / 1024; pc += C::NW)
-      blds16(rN, (MK_LDS void*)(cn_lds + pc * 1024), loff, (uint32_t)pc * 1024u);
+    cn_issue<C>(rN, cn_lds, cn_bytes, wid, loff);
 #pragma unroll
     for (int j = 0; j < EJ; ++j) xg[j] = a.xn[row_of(4 * j + g < C::P ? 4 * j + g : C::P - 1)];
     __builtin_amdgcn_sched_barrier(0);
@@ -277,14 +245,12 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
     }
   }
   // per-wave (inertia, changed) totals, in LDS after the offsets
-  double* wacc = (double*)(bufs + C::NBUF * C::CHUNK_BYTES + 16 * C::NW + C::OPT_BYTES);
+  double* wacc = L.wacc();
   {
     // |c|^2 and the first centre chunk by LDS-DMA, issued after the fragments so no wait for a
     // fragment address (the gathered row indices) also waits for them.
     __builtin_amdgcn_sched_barrier(0);
-    if (!early)
-      for (int p = wid; p < cn_bytes / 1024; p += C::NW)
-        blds16(rN, (MK_LDS void*)(cn_lds + p * 1024), loff, (uint32_t)p * 1024u);
+    if (!early) cn_issue<C>(rN, cn_lds, cn_bytes, wid, loff);
     issue_chunk(0, 0);
     unsigned long long t_frag = 0ull;
     if (early) {
@@ -299,20 +265,13 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
       wait_vmcnt<0>();  // retire the fragments before the LDS-DMA loop (its vmcnt waits count chunks)
     }
     const unsigned long long t_landed = a.timeline ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    if (C::NBUF == 3 && ncl > 1) issue_chunk(1, 1);
 
-    // bf16 seed offset (see the header): o = (1 + 2^-12) max |x|^2 over the workgroup's
-    // points, from the caller's row norms when given (loaded with the fragments) or from
-    // the fragments themselves, folded into this workgroup's LDS copy of |c|^2 once.
-    // A workgroup whose max |x|^2 exceeds 4x its min (an outlier row, or data around the
-    // origin) takes per-point offsets o_p = (1 + 2^-12) |x_p|^2 instead, parked in LDS and
-    // added to each tile's seed (second chunk-loop instantiation): a shared offset would coarsen every
-    // neighbour's keys to 2^-17 of the outlier's norm.  Either way a key resolves
-    // 2^-17 (|x - c|^2 + 3 |x|^2) or better.
+    // bf16 seed offset (see the header): from the caller's row norms when given (loaded with the fragments)
+    // or from the fragments.  Per-point offsets o_p = (1 + 2^-12) |x_p|^2 are parked in LDS and added to each
+    // tile's seed (second chunk-loop instantiation); either way a key resolves 2^-17 (|x - c|^2 + 3 |x|^2).
     float off = 0.f;
     bool ppo = false;
-    float* opt = (float*)(bufs + C::NBUF * C::CHUNK_BYTES + 16 * C::NW);  // [NW][16][PP] offsets
-    float* xnl = opt + C::NW * 16 * C::PP;                                 // [NW][16][PP] |x|^2
+    float *opt = L.opt(), *xnl = L.xnl();   // [NW][16][PP] offsets, |x|^2
     if (!a.xn && (!F32 || a.slots)) {
 #pragma unroll
       for (int p = 0; p < C::P; ++p) {
@@ -325,7 +284,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
       }
       if (a.slots && g == 0) {   // no caller norms: the epilogue's inertia reads them back
 #pragma unroll
-        for (int p = 0; p < C::P; ++p) xnl[(wid * 16 + r) * C::PP + p] = xnr[p];
+        for (int p = 0; p < C::P; ++p) xnl[L.row(wid, r) + p] = xnr[p];
       }
     }
     if constexpr (!F32) {
@@ -336,7 +295,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
       ppo = true;
       if (g == 0) {
 #pragma unroll
-        for (int p = 0; p < C::P; ++p) opt[(wid * 16 + r) * C::PP + p] = osr[p];
+        for (int p = 0; p < C::P; ++p) opt[L.row(wid, r) + p] = osr[p];
       }
      } else {
       float m = 0.f, mn = 3.0e38f;
@@ -356,18 +315,20 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
         m = fmaxf(m, __shfl_xor(m, o, 64));
         mn = fminf(mn, __shfl_xor(mn, o, 64));
       }
-      float* red = (float*)(bufs + C::NBUF * C::CHUNK_BYTES);
+      float* red = L.red();
       if (lane == 0) { red[2 * wid] = m; red[2 * wid + 1] = mn; }
       // every wave's |c|^2 DMA has landed (its wait above); a raw barrier, so an early
       // prologue's fragments and first chunk stay in flight (__syncthreads drains vmcnt)
       wait_lgkm0();
       raw_barrier();
+      // The seed rule; it stands again in assign16_persist_kernel, line for line but for the thread id and
+      // the parking -- change both (as a function it moved every bf16 kernel's registers, profiles/r14_01).
       float mnw = 3.0e38f;
 #pragma unroll
       for (int w = 0; w < C::NW; ++w) { off = fmaxf(off, red[2 * w]); mnw = fminf(mnw, red[2 * w + 1]); }
       ppo = __builtin_amdgcn_readfirstlane((int)(off > 4.f * mnw)) != 0;
       if (!ppo) {
-        off = __builtin_fmaf(off, 2.44140625e-04f, off);  // * (1 + 2^-12)
+        off = seed_scale(off);
         off = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(off)));
         for (int k = threadIdx.x; k < a.Kpad; k += C::NW * 64) ((float*)cn_lds)[k] += off;
       } else {
@@ -375,10 +336,10 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
         if (early) {
 #pragma unroll
           for (int j = 0; j < EJ; ++j)
-            if (4 * j + g < C::P) opt[(wid * 16 + r) * C::PP + 4 * j + g] = __builtin_fmaf(xg[j], 2.44140625e-04f, xg[j]);
+            if (4 * j + g < C::P) opt[L.row(wid, r) + 4 * j + g] = seed_scale(xg[j]);
         } else if (g == 0) {
 #pragma unroll
-          for (int p = 0; p < C::P; ++p) opt[(wid * 16 + r) * C::PP + p] = __builtin_fmaf(xnr[p], 2.44140625e-04f, xnr[p]);
+          for (int p = 0; p < C::P; ++p) opt[L.row(wid, r) + p] = seed_scale(xnr[p]);
         }
       }
      }
@@ -410,14 +371,13 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
     auto chunk_loop = [&](auto ppo_tag) {
       constexpr bool PPO = decltype(ppo_tag)::value;
       for (int c = 0; c < ncl; ++c) {
-        // chunk c landed; with 3 slots chunk c+1 may stay in flight across the barrier
-        if (C::NBUF == 3 && c + 1 < ncl) wait_vmcnt<C::NPW>(); else wait_vmcnt<0>();
+        wait_vmcnt<0>();   // chunk c landed
         wait_lgkm0();
         raw_barrier();  // RAW for chunk c, WAR for the slot refilled next (read at c-1)
         // (the next chunk's pieces all go out right after the barrier: spreading them one group
         // per tile after that tile's epilogue measured -2.5 % at D=128, -5 % at D=256 and far
         // slower at D=64, profiles/r3_28_ab_spread_dma.log)
-        if (c + C::NBUF - 1 < ncl) issue_chunk(c + C::NBUF - 1, (c + C::NBUF - 1) % C::NBUF);
+        if (c + 1 < ncl) issue_chunk(c + 1, (c + 1) % C::NBUF);
         const char* buf = bufs + (c % C::NBUF) * C::CHUNK_BYTES;
         // A fragments + |c|^2 of a tile from the LDS ring
         auto load_a = [&](int tl_i, u32x4* aw_, f32x4& ci_) {
@@ -429,19 +389,19 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
             for (int q = 0; q < C::NQ; ++q) aw_[q] = *(const u32x4*)(tl + q * 1024);
           }
         };
-        // EARLY (bf16 D=64): the next tile's fragments are read right after this tile's
+        // A_AHEAD (bf16 D=64): the next tile's fragments are read right after this tile's
         // MFMAs are issued, so their LDS latency hides under the argmin epilogue (+2 % at D=64
         // in one-process A/B, profiles/r2_08_assign_clock_study.md; no gain at D=128)
-        constexpr bool EARLY = !F32 && DPAD == 64;
+        constexpr bool A_AHEAD = !F32 && DPAD == 64;
         u32x4 awe[C::NQ];
         f32x4 cie;
-        if constexpr (EARLY) load_a(0, awe, cie);
+        if constexpr (A_AHEAD) load_a(0, awe, cie);
     #pragma unroll
         for (int tl_i = 0; tl_i < C::CT; ++tl_i) {
           const int tile = (c0 + c) * C::CT + tl_i;
           u32x4 aw[C::NQ];
           f32x4 ci;
-          if constexpr (EARLY) {
+          if constexpr (A_AHEAD) {
     #pragma unroll
             for (int q = 0; q < C::NQ; ++q) aw[q] = awe[q];
             ci = cie;
@@ -449,43 +409,11 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
             load_a(tl_i, aw, ci);
           }
           f32x4 acc[C::P];
-    #pragma unroll
-          for (int p = 0; p < C::P; ++p) acc[p] = ci;
-          if constexpr (PPO) {  // per-point offsets seed the accumulators (one LDS read per tile)
-            // (added BEFORE the MFMAs: VALU writes the MFMA then reads as src C.  Adding them
-            // to the MFMA results instead raced the matrix pipe: a v_pk_add_f32 read the
-            // result registers early when the LDS read ahead of it returned fast, a rare,
-            // nondeterministic wrong label, tests/test_gpu_kernels.py split-batch test)
-            const float* o = opt + (wid * 16 + r) * C::PP;
-    #pragma unroll
-            for (int p4 = 0; p4 < C::P; p4 += 4) {
-              const f32x4 ov = *(const f32x4*)(o + p4);
-    #pragma unroll
-              for (int j = 0; j < 4; ++j)
-                if (p4 + j < C::P) seed_add(acc[p4 + j], ov[j]);
-            }
-          }
-          // bf16: the wave issues its MFMAs at raised priority and drops back for the epilogue,
-          // so a SIMD's arbiter feeds the matrix core before another wave's argmin VALU work
-          // (profiles/r2_29_assign_setprio_ab.log, one process each: the harness copy -2.2 % at
-          // D=128 K=1024 and -1.4 % at D=64 K=4096; this kernel against that copy +0.8 % at D=128,
-          // +0.3 % at D=64, about +5 % at D=256 K=512)
-          if constexpr (!F32) {
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(1);
-            __builtin_amdgcn_sched_barrier(0);
-          }
+          seed_tile<C, PPO ? 1 : 0>(acc, ci, opt + L.row(wid, r));
+          mfma_priority<T, 1>();
           // per-block argmin epilogue (bf16): packed 6-bit keys or the value-only running minimum
           unsigned t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-          if constexpr (!EXACT && !VARG) {
-            // 6-bit keys over a segment of 16 tiles (tile-in-segment * 4 + reg): 4 key packs
-            // + 2 v_min3 per tile and point block; the running best is merged with its
-            // segment id once per segment.  The four indices as opaque SGPRs, so each key is
-            // one v_and_or_b32.
-            const unsigned tis = (unsigned)(tile & 15) << 2;
-            asm volatile("s_mov_b32 %0, %4\n\ts_or_b32 %1, %4, 1\n\ts_or_b32 %2, %4, 2\n\ts_or_b32 %3, %4, 3"
-                         : "=s"(t0), "=s"(t1), "=s"(t2), "=s"(t3) : "s"(tis) : "scc");  // s_or_b32 writes SCC
-          }
+          if constexpr (!EXACT && !VARG) key6_indices((unsigned)(tile & 15) << 2, t0, t1, t2, t3);
           auto epi = [&](int p) {
             if constexpr (VARG) {
               // scores are positive (seed offset, see the header), so they order as their bits;
@@ -495,32 +423,18 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
               const uint32_t nb = min(min(u0, u1), min(u2, min(u3, vb[p])));
               tb[p] = nb != vb[p] ? (uint32_t)tile : tb[p];
               vb[p] = nb;
-            } else {
+            } else if constexpr (TOP2) {
+              // the segment's sorted pair (seg_best, m2s): med3 (asm, see common.h) of it and a key is the new second
               const f32x4& sv = acc[p];
-              const float k0 = pack_key6(sv[0], kmask, t0), k1 = pack_key6(sv[1], kmask, t1);
-              const float k2 = pack_key6(sv[2], kmask, t2), k3 = pack_key6(sv[3], kmask, t3);
-              if constexpr (TOP2) {
-                // the segment's sorted pair (seg_best, m2s): med3 of (smallest, second, new) is
-                // the new second
-                // (asm forms: no per-key canonicalisation, see common.h med3f)
-                m2s[p] = med3f(seg_best[p], m2s[p], k0);
-                seg_best[p] = min2f(seg_best[p], k0);
-                m2s[p] = med3f(seg_best[p], m2s[p], k1);
-                seg_best[p] = min2f(seg_best[p], k1);
-                m2s[p] = med3f(seg_best[p], m2s[p], k2);
-                seg_best[p] = min2f(seg_best[p], k2);
-                m2s[p] = med3f(seg_best[p], m2s[p], k3);
-                seg_best[p] = min2f(seg_best[p], k3);
-              } else {
-                seg_best[p] = min3f(min3f(k0, k1, k2), k3, seg_best[p]);
+              const float k[4] = {pack_key6(sv[0], kmask, t0), pack_key6(sv[1], kmask, t1), pack_key6(sv[2], kmask, t2),
+                                  pack_key6(sv[3], kmask, t3)};
+#pragma unroll
+              for (int e = 0; e < 4; ++e) {
+                m2s[p] = med3f(seg_best[p], m2s[p], k[e]);
+                seg_best[p] = min2f(seg_best[p], k[e]);
               }
-            }
-          };
-          auto chain = [&](int p) {   // block p's NQ MFMAs back to back (srcC = the previous vDst)
-    #pragma unroll
-            for (int q = 0; q < C::NQ; ++q) {
-              acc[p] = Mfma16<T>::run(aw[q], xr[p][q], acc[p]);
-              __builtin_amdgcn_sched_barrier(0);
+            } else {
+              key6_fold(acc[p], kmask, t0, t1, t2, t3, seg_best[p]);
             }
           };
           if constexpr (WIDE) {
@@ -546,23 +460,26 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
               for (int p = 0; p < C::P; ++p) acc[p] = Mfma16<T>::run(aq[q], xr[p][q], acc[p]);
               __builtin_amdgcn_sched_barrier(0);
             }
-          } else if constexpr (PMAJ) {
-            // point-block-major issue, pinned in this order
-#pragma unroll
-            for (int p = 0; p < C::P; ++p) chain(p);
           } else {
+            // The tile's MFMAs; the same text stands in assign16_persist_kernel's run_tile: change both (as a function it
+            // put s_nops into the VARG loops).  PMAJ: each block's NQ back to back, pinned; else piece-major.
+            if constexpr (PMAJ) {
 #pragma unroll
-            for (int q = 0; q < C::NQ; ++q) {
+              for (int p = 0; p < C::P; ++p)
 #pragma unroll
-              for (int p = 0; p < C::P; ++p) acc[p] = Mfma16<T>::run(aw[q], xr[p][q], acc[p]);
+                for (int q = 0; q < C::NQ; ++q) {
+                  acc[p] = Mfma16<T>::run(aw[q], xr[p][q], acc[p]);
+                  __builtin_amdgcn_sched_barrier(0);
+                }
+            } else {
+#pragma unroll
+              for (int q = 0; q < C::NQ; ++q)
+#pragma unroll
+                for (int p = 0; p < C::P; ++p) acc[p] = Mfma16<T>::run(aw[q], xr[p][q], acc[p]);
             }
           }
-          if constexpr (!F32) {
-            __builtin_amdgcn_sched_barrier(0);
-            __builtin_amdgcn_s_setprio(0);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          if constexpr (EARLY) {
+          mfma_priority<T, 0>();
+          if constexpr (A_AHEAD) {
             if (tl_i + 1 < C::CT) load_a(tl_i + 1, awe, cie);
             __builtin_amdgcn_sched_barrier(0);
           }
@@ -591,12 +508,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
                   m2[p] = min3f(m2[p], m2s[p], max2f(best[p], seg_best[p]));
                   m2s[p] = 3.0e38f;
                 }
-                // compare values only: on equal (truncated) values the earlier segment keeps
-                // the lower centroid index (all keys are >= 0, see the header)
-                const float sv = __uint_as_float(__float_as_uint(seg_best[p]) & ~63u);
-                const float bv = __uint_as_float(__float_as_uint(best[p]) & ~63u);
-                if (sv < bv) { best[p] = seg_best[p]; bg[p] = tile >> 4; }
-                seg_best[p] = 3.0e38f;
+                key6_segment_merge(best[p], bg[p], seg_best[p], tile);
               }
             }
           }
@@ -611,9 +523,8 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
       tl[0] = t_entry;
       tl[1] = t_loop;
       tl[2] = __builtin_amdgcn_s_memrealtime();
-      tl[4] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_ID
-      tl[5] = (unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));   // XCC_ID
-      tl[6] = t_landed;   // fragments, |c|^2 and the first chunk landed (wave 0)
+      timeline_ids(tl);
+      tl[6] = t_landed;  // fragments, |c|^2 and the first chunk landed (wave 0)
       tl[7] = early ? t_issued : t_frag;   // early prologue: the loads' issue completed; else
                                            // (Kpad <= 1024, 4 chunk pieces per wave) the fragments landed
     }
@@ -630,11 +541,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
 #pragma unroll
       for (int p = 0; p < C::P; ++p) {
         uint32_t v = vb[p], tg = tb[p] * 4u + (uint32_t)g;
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-          const uint32_t vo = (uint32_t)__shfl_xor((int)v, o, 64), to = (uint32_t)__shfl_xor((int)tg, o, 64);
-          if (vo < v || (vo == v && to < tg)) { v = vo; tg = to; }
-        }
+        merge_groups(v, tg, ShflXor{});
         vb[p] = v;
         tb[p] = tg;
       }
@@ -661,7 +568,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
             const uint32_t tgs = (uint32_t)__shfl((int)tb[p], 4 * m + g, 64);     // output rows' point
             acc[mi] = *(const f32x4*)(cn_lds + ((int)(tgs >> 2) * 16 + (int)(tgs & 3u) * 4) * 4);
             if (ppo) {
-              seed_add(acc[mi], opt[(wid * 16 + r) * C::PP + p]);
+              seed_add(acc[mi], opt[L.row(wid, r) + p]);
             }
           }
 #pragma unroll
@@ -697,18 +604,10 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
         if constexpr (EXACT) {  // bg = tile * 4 + reg of the first strict minimum
           k = (bg[p] >> 2) * 16 + 4 * g + (bg[p] & 3);
           v = best[p];
-        } else {               // bg = segment of 16 tiles, 6-bit key; undo the seed offset
-          const unsigned bits = __float_as_uint(best[p]);
-          const int idx = (int)(bits & 63u);
-          k = (bg[p] * 16 + (idx >> 2)) * 16 + 4 * g + (idx & 3);
-          v = __uint_as_float(bits & ~63u);
+        } else {               // bg = segment of 16 tiles, 6-bit key
+          key6_decode(best[p], bg[p], g, v, k);
         }
-#pragma unroll
-        for (int o = 16; o <= 32; o <<= 1) {
-          const float vo = __shfl_xor(v, o, 64);
-          const int ko = __shfl_xor(k, o, 64);
-          if (vo < v || (vo == v && ko < k)) { v = vo; k = ko; }
-        }
+        merge_groups(v, k, ShflXor{});
       }
     };
     float inert = 0.f;
@@ -731,9 +630,9 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
     // ``old``: the row's previous label, ``xnv``: its caller norm (read by the caller of this
     // lambda, i < N, lanes with (p & 3) == g only); ``sec``: the second-smallest score (TOP2)
     auto store = [&](int p, int64_t oi, int k, float v, int old, float xnv, float sec) {
-      const float offp = ppo ? opt[(wid * 16 + r) * C::PP + p] : off;   // the seed offset (0: f32)
+      const float offp = ppo ? opt[L.row(wid, r) + p] : off;   // the seed offset (0: f32)
       // inertia without caller norms: the prologue parked |x|^2 of the fragments in LDS
-      const float xv = (a.slots && !a.xn) ? xnl[(wid * 16 + r) * C::PP + p] : xnv;
+      const float xv = (a.slots && !a.xn) ? xnl[L.row(wid, r) + p] : xnv;
       if (a.split_keys) {
         // compare the (positive) keys across splits; split_finish undoes the offset
         // (parked in mind[], which the caller provides whenever xn is given)
@@ -776,10 +675,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
     if (a.slots && !a.split_keys) {   // the wave's totals, in its LDS slot
       const double di = wave_sum((double)inert);
       const int dc = wave_sum(changed);
-      if (lane == 0) {
-        wacc[2 * wid] = di;
-        wacc[2 * wid + 1] = (double)dc;
-      }
+      if (lane == 0) { wacc[2 * wid] = di; wacc[2 * wid + 1] = (double)dc; }
     }
   }
   if (a.timeline && threadIdx.x == 0 && blockIdx.y == 0)
@@ -789,12 +685,7 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
     // vmcnt, i.e. wait for every label / distance store of the epilogue to be acknowledged
     wait_lgkm0();
     raw_barrier();
-    if (threadIdx.x == 0) {
-      double si = 0, sc = 0;
-#pragma unroll
-      for (int w = 0; w < C::NW; ++w) { si += wacc[2 * w]; sc += wacc[2 * w + 1]; }
-      slot_add((unsigned long long*)(a.slots + (blockIdx.x % NSLOT) * SLOT_STRIDE), si, (long long)sc);
-    }
+    if (threadIdx.x == 0) slot_add_totals<C>(wacc, a.slots + (blockIdx.x % NSLOT) * SLOT_STRIDE);
   }
 }
 
@@ -823,6 +714,14 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
 constexpr int PERSIST_CTR_SLOTS = 64;
 __device__ unsigned g_persist_ctr[PERSIST_CTR_SLOTS][2];
 
+// lane ^ o shuffles on a laundered lane id ln (fresh_tid below): the library forms' addresses are
+// loop invariants, which the compiler hoisted out of the group loop and spilled
+struct ShflLaundered {
+  int ln;
+  __device__ __forceinline__ int operator()(int v, int o) const { return __builtin_amdgcn_ds_bpermute((ln ^ o) << 2, v); }
+  __device__ __forceinline__ float operator()(float v, int o) const { return __int_as_float((*this)(__float_as_int(v), o)); }
+};
+
 template <int DPAD, int P, int OCC, int PMAJ>
 __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a, int ngroups, int cslot) {
   using T = uint16_t;
@@ -835,35 +734,22 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, g = lane >> 4;
-  const int cn_bytes = ((a.Kpad * 4 + 1023) / 1024) * 1024;
-  char* cn_lds = smem;
-  char* bufs = smem + cn_bytes;
+  const AssignLds<C> L(smem, a.Kpad);
+  const int cn_bytes = L.cn_bytes(a.Kpad);
+  char *cn_lds = L.cn, *bufs = L.ring;
   const int ncl = a.Kpad / (16 * C::CT);
   const uint32_t loff = (uint32_t)lane * 16u;
   const __amdgpu_buffer_rsrc_t rC = make_rsrc(a.Cpack, (uint32_t)a.Kpad * DPAD * sizeof(T));
-  auto issue_chunk = [&](int c, int slot) {
-    const uint32_t src = (uint32_t)c * C::CHUNK_BYTES;
-    char* dst = bufs + slot * C::CHUNK_BYTES;
-#pragma unroll
-    for (int i = 0; i < C::NPW; ++i) {
-      const int pc = wid + i * C::NW;
-      blds16(rC, (MK_LDS void*)(dst + pc * 1024), loff, src + (uint32_t)pc * 1024u);
-    }
-  };
+  auto issue_chunk = [&](int c, int slot) { ring_issue<C>(rC, bufs, slot, c, wid, loff); };
   const int64_t N = a.N;
-  // (the LDS layout of assign16_kernel: min / max scratch, per-point offsets, wave totals)
-  float* red = (float*)(bufs + C::NBUF * C::CHUNK_BYTES);
-  float* opt = (float*)(bufs + C::NBUF * C::CHUNK_BYTES + 16 * C::NW);
-  double* wacc = (double*)(bufs + C::NBUF * C::CHUNK_BYTES + 16 * C::NW + C::OPT_BYTES);
-  // one norm (the gathered-norm half of the offsets area, unused with caller norms) and one old
-  // label (PERSIST_LDS_EXTRA bytes behind the wave totals) per thread, landed by LDS-DMA
-  uint32_t* xg_lds = (uint32_t*)(opt + C::NW * 16 * C::PP);
-  uint32_t* el_lds = (uint32_t*)(bufs + C::NBUF * C::CHUNK_BYTES + 16 * C::NW + C::OPT_BYTES + 16 * C::NW);
+  float *red = L.red(), *opt = L.opt();
+  double* wacc = L.wacc();
+  uint32_t *xg_lds = L.xg(), *el_lds = L.old_labels();   // one norm, one old label per thread, landed by LDS-DMA
   const unsigned kmask = key6_mask();
   const int G = (int)gridDim.x;
   int grp = (int)blockIdx.x;   // the first group; the others come from the launch's group counter
   unsigned* ctr = g_persist_ctr[cslot];
-  int* nxt_lds = (int*)(red + 2 * C::NW);   // the next group, handed from thread 0 to the workgroup
+  int* nxt_lds = L.next_group();   // the next group, handed from thread 0 to the workgroup
   int s0 = 0;   // ring slot of this pass's chunk 0 (alternates when a pass has an odd chunk count)
 
   // A lane's part of every row, norm and label address is one 32-bit offset inside the group
@@ -881,9 +767,6 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
     asm volatile("" : "+v"(t));
     return t;
   };
-  // lane ^ o shuffles on a laundered lane id (the library forms' addresses are loop invariants too)
-  auto sx = [](int ln, int v, int o) -> int { return __builtin_amdgcn_ds_bpermute((ln ^ o) << 2, v); };
-  auto sxf = [&](int ln, float v, int o) -> float { return __int_as_float(sx(ln, __float_as_int(v), o)); };
   auto lrow_of = [&](int tid, int p) -> int { return wid * (C::P * 16) + p * 16 + (tid & 15); };   // row in the group
 
   // The prefetched fragment loads are inline asm, tied to the registers that hold the current
@@ -939,11 +822,7 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
   // |c|^2 by LDS-DMA: the seed offset is folded into the LDS copy per group, so every group
   // starts from a fresh copy (4 KiB at K = 1024; a pristine second copy does not fit the LDS
   // of four workgroups)
-  auto issue_cn = [&]() {
-    const __amdgpu_buffer_rsrc_t rN = make_rsrc(a.cn, (uint32_t)a.Kpad * 4u);
-    for (int pc = wid; pc < cn_bytes / 1024; pc += C::NW)
-      blds16(rN, (MK_LDS void*)(cn_lds + pc * 1024), loff, (uint32_t)pc * 1024u);
-  };
+  auto issue_cn = [&]() { cn_issue<C>(make_rsrc(a.cn, (uint32_t)a.Kpad * 4u), cn_lds, cn_bytes, wid, loff); };
   issue_cn();
   issue_chunk(0, 0);
   load_group(grp);
@@ -961,7 +840,7 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
     if (a.timeline && threadIdx.x == 0) a.timeline[(int64_t)grp * 8 + 6] = __builtin_amdgcn_s_memrealtime();
     float exn[EJ];   // the epilogue's norms (xg takes the next group's under the epilogue)
     exn[0] = __uint_as_float(xg_lds[fresh_tid()]);   // (this wave's own DMA, retired by the wait above)
-    // seed offset, or per-point offsets, of this group (see assign16_kernel)
+    // seed offset, or per-point offsets, of this group: its own wave reduction, then the shared rule
     float off = 0.f;
     bool ppo = false;
     unsigned fetched;
@@ -969,23 +848,26 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
       const int ttid = fresh_tid();
       fetched = 0u;
       const int tln = ttid & 63, tr = ttid & 15, tg = tln >> 4;
+      const ShflLaundered sh{tln};
       float m = 0.f, mn = 3.0e38f;
 #pragma unroll
       for (int j = 0; j < EJ; ++j) { m = fmaxf(m, exn[j]); mn = fminf(mn, exn[j]); }
-      m = fmaxf(m, sxf(tln, m, 16));
-      mn = fminf(mn, sxf(tln, mn, 16));
-      m = fmaxf(m, sxf(tln, m, 32));
-      mn = fminf(mn, sxf(tln, mn, 32));
+      m = fmaxf(m, sh(m, 16));
+      mn = fminf(mn, sh(mn, 16));
+      m = fmaxf(m, sh(m, 32));
+      mn = fminf(mn, sh(mn, 32));
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) {
-        m = fmaxf(m, sxf(tln, m, o));
-        mn = fminf(mn, sxf(tln, mn, o));
+        m = fmaxf(m, sh(m, o));
+        mn = fminf(mn, sh(mn, o));
       }
       if (tln == 0) { red[2 * wid] = m; red[2 * wid + 1] = mn; }
       // every wave is past the previous group's chunk loop and label epilogue here: |c|^2,
       // the offsets and the wave totals in LDS may be rewritten behind this barrier
       wait_lgkm0();
       raw_barrier();
+      // (every wave's |c|^2 pieces landed before the barrier above)
+      // The seed rule; it stands again in assign16_kernel, line for line but for thread id and parking: change both.
       float mnw = 3.0e38f;
 #pragma unroll
       for (int w = 0; w < C::NW; ++w) { off = fmaxf(off, red[2 * w]); mnw = fminf(mnw, red[2 * w + 1]); }
@@ -993,15 +875,14 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
       // the next group: one returning atomic per group, a whole chunk loop ahead of its use
       if (ttid == 0) fetched = atomicAdd(ctr, 1u);
       if (!ppo) {
-        off = __builtin_fmaf(off, 2.44140625e-04f, off);  // * (1 + 2^-12)
+        off = seed_scale(off);
         off = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(off)));
-        // (every wave's |c|^2 pieces landed before the barrier above)
         for (int kk = ttid; kk < a.Kpad; kk += C::NW * 64) ((float*)cn_lds)[kk] += off;
       } else {
         off = 0.f;
 #pragma unroll
         for (int j = 0; j < EJ; ++j)
-          if (4 * j + tg < C::P) opt[(wid * 16 + tr) * C::PP + 4 * j + tg] = __builtin_fmaf(exn[j], 2.44140625e-04f, exn[j]);
+          if (4 * j + tg < C::P) opt[L.row(wid, tr) + 4 * j + tg] = seed_scale(exn[j]);
       }
     }
 
@@ -1049,61 +930,34 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
 #pragma unroll
       for (int q = 0; q < C::NQ; ++q) aw[q] = *(const u32x4*)(tl + q * 1024);
       f32x4 acc[C::P];
-#pragma unroll
-      for (int p = 0; p < C::P; ++p) acc[p] = ci;
-      if (PPO == 1 || (PPO == 2 && ppo)) {  // (added BEFORE the MFMAs, see assign16_kernel)
-        const float* o = opt + (wid * 16 + r) * C::PP;
-#pragma unroll
-        for (int p4 = 0; p4 < C::P; p4 += 4) {
-          const f32x4 ov = *(const f32x4*)(o + p4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (p4 + j < C::P) seed_add(acc[p4 + j], ov[j]);
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-      __builtin_amdgcn_sched_barrier(0);
+      seed_tile<C, PPO>(acc, ci, opt + L.row(wid, r), ppo);
+      mfma_priority<T, 1>();
       unsigned t0 = 0, t1 = 0, t2 = 0, t3 = 0;
-      const unsigned tis = (unsigned)(tile & 15) << 2;
-      asm volatile("s_mov_b32 %0, %4\n\ts_or_b32 %1, %4, 1\n\ts_or_b32 %2, %4, 2\n\ts_or_b32 %3, %4, 3"
-                   : "=s"(t0), "=s"(t1), "=s"(t2), "=s"(t3) : "s"(tis) : "scc");
+      key6_indices((unsigned)(tile & 15) << 2, t0, t1, t2, t3);
+      // The tile's MFMAs; the same text stands in assign16_kernel's chunk loop: change both (as a function it
+      // put s_nops into the VARG loops).  PMAJ: each block's NQ back to back, pinned; else piece-major.
       if constexpr (PMAJ) {
 #pragma unroll
-        for (int p = 0; p < C::P; ++p) {
+        for (int p = 0; p < C::P; ++p)
 #pragma unroll
           for (int q = 0; q < C::NQ; ++q) {
             acc[p] = Mfma16<T>::run(aw[q], xr[p][q], acc[p]);
             __builtin_amdgcn_sched_barrier(0);
           }
-        }
       } else {
 #pragma unroll
-        for (int q = 0; q < C::NQ; ++q) {
+        for (int q = 0; q < C::NQ; ++q)
 #pragma unroll
           for (int p = 0; p < C::P; ++p) acc[p] = Mfma16<T>::run(aw[q], xr[p][q], acc[p]);
-        }
       }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
+      mfma_priority<T, 0>();
       // the pass's last MFMAs are issued: the fragment registers take the next group's rows
       if constexpr (FINAL) load_group(nxt);
 #pragma unroll
-      for (int p = 0; p < C::P; ++p) {
-        const f32x4& sv = acc[p];
-        const float k0 = pack_key6(sv[0], kmask, t0), k1 = pack_key6(sv[1], kmask, t1);
-        const float k2 = pack_key6(sv[2], kmask, t2), k3 = pack_key6(sv[3], kmask, t3);
-        seg_best[p] = min3f(min3f(k0, k1, k2), k3, seg_best[p]);
-      }
+      for (int p = 0; p < C::P; ++p) key6_fold(acc[p], kmask, t0, t1, t2, t3, seg_best[p]);
       if (FINAL || (tile & 15) == 15) {
 #pragma unroll
-        for (int p = 0; p < C::P; ++p) {
-          const float sv = __uint_as_float(__float_as_uint(seg_best[p]) & ~63u);
-          const float bv = __uint_as_float(__float_as_uint(best[p]) & ~63u);
-          if (sv < bv) { best[p] = seg_best[p]; bg[p] = tile >> 4; }
-          seg_best[p] = 3.0e38f;
-        }
+        for (int p = 0; p < C::P; ++p) key6_segment_merge(best[p], bg[p], seg_best[p], tile);
       }
     };
     auto chunk_loop = [&](auto ppo_tag) {
@@ -1124,8 +978,7 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
     if (a.timeline && threadIdx.x == 0) {
       unsigned long long* tl = a.timeline + (int64_t)grp * 8;
       tl[2] = __builtin_amdgcn_s_memrealtime();
-      tl[4] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));    // HW_ID
-      tl[5] = (unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));   // XCC_ID
+      timeline_ids(tl);
     }
 
     // The group's label epilogue: assign16_kernel's, packed keys with caller norms
@@ -1136,25 +989,20 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
     const int etid = fresh_tid();
     const int eold = (int)el_lds[etid];
     const int eln = etid & 63, er = etid & 15, eg = eln >> 4;
+    const ShflLaundered esh{eln};
     // (descriptors over the group's valid rows: no store can leave them)
     const __amdgpu_buffer_rsrc_t rL = make_rsrc(a.labels + (int64_t)grp * C::PTS, (uint32_t)nvc * 4u);
     const __amdgpu_buffer_rsrc_t rM = make_rsrc(a.mind ? a.mind + (int64_t)grp * C::PTS : nullptr,
                                                 a.mind ? (uint32_t)nvc * 4u : 0u);
 #pragma unroll
     for (int p = 0; p < C::P; ++p) {
-      const unsigned bits = __float_as_uint(best[p]);
-      const int idx = (int)(bits & 63u);
-      int k = (bg[p] * 16 + (idx >> 2)) * 16 + 4 * eg + (idx & 3);
-      float v = __uint_as_float(bits & ~63u);
-#pragma unroll
-      for (int o = 16; o <= 32; o <<= 1) {
-        const float vo = sxf(eln, v, o);
-        const int ko = sx(eln, k, o);
-        if (vo < v || (vo == v && ko < k)) { v = vo; k = ko; }
-      }
+      int k;
+      float v;   // (the one-pass kernel's decode and merge, on the laundered lane id)
+      key6_decode(best[p], bg[p], eg, v, k);
+      merge_groups(v, k, esh);
       const int lr = lrow_of(etid, p);
       if ((p & 3) == eg && lr < nvc) {
-        const float offp = ppo ? opt[(wid * 16 + er) * C::PP + p] : off;
+        const float offp = ppo ? opt[L.row(wid, er) + p] : off;
         v -= offp;   // back to |c|^2 - 2 x.c
         if (a.track_changed) changed += (eold != k);
         __builtin_amdgcn_raw_buffer_store_b32((unsigned)k, rL, (uint32_t)lr * 4u, 0, 0);
@@ -1170,14 +1018,11 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) {
         const long long b = __double_as_longlong(di);
-        const int lo = sx(eln, (int)(unsigned)b, o), hi = sx(eln, (int)(b >> 32), o);
+        const int lo = esh((int)(unsigned)b, o), hi = esh((int)(b >> 32), o);
         di += __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-        dc += sx(eln, dc, o);
+        dc += esh(dc, o);
       }
-      if (eln == 0) {
-        wacc[2 * wid] = di;
-        wacc[2 * wid + 1] = (double)dc;
-      }
+      if (eln == 0) { wacc[2 * wid] = di; wacc[2 * wid + 1] = (double)dc; }
     }
     if (a.timeline && threadIdx.x == 0) {
       const unsigned long long t = __builtin_amdgcn_s_memrealtime();
@@ -1194,12 +1039,7 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
     if (has_next) issue_cn();
     if (a.slots) {
       // one slot_add per group, the one-pass workgroup's addends and slot
-      if (threadIdx.x == 0) {
-        double si = 0, sc = 0;
-#pragma unroll
-        for (int w = 0; w < C::NW; ++w) { si += wacc[2 * w]; sc += wacc[2 * w + 1]; }
-        slot_add((unsigned long long*)(a.slots + (grp % NSLOT) * SLOT_STRIDE), si, (long long)sc);
-      }
+      if (threadIdx.x == 0) slot_add_totals<C>(wacc, a.slots + (grp % NSLOT) * SLOT_STRIDE);
     }
     if (!has_next) break;
     grp = nxt;
@@ -1265,26 +1105,21 @@ static int assign16_splits(int64_t nblk, int nch) {
 // D=64 K=2048 +8.5 %, K=1024 -3.7 %; D=32 K=1024 +5.6 %, K=512 -8.8 %).
 // Variant V_ASSIGN_VARG = 0/1 forces it off / on (A/B, tests).
 
-template <typename T, int DPAD, int P, int CT_, int NBUF_, int OCC, int NW_, bool VARG, int PMAJ, bool TOP2, bool XV>
-static void set_lds_attr() {
-  static bool done = false;
-  if (done) return;
-  (void)hipFuncSetAttribute((const void*)assign16_kernel<T, DPAD, P, CT_, NBUF_, OCC, NW_, false, VARG, PMAJ, TOP2, XV>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  (void)hipFuncSetAttribute((const void*)assign16_kernel<T, DPAD, P, CT_, NBUF_, OCC, NW_, true, VARG, PMAJ, TOP2, XV>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  done = true;
-}
+// The epilogue a launch runs, as a tag (assign16_kernel's trailing template arguments)
+template <bool VARG_, int PMAJ_, bool TOP2_, bool XV_, bool FULLD_>
+struct Epi {
+  static constexpr bool VARG = VARG_, TOP2 = TOP2_, XV = XV_, FULLD = FULLD_;
+  static constexpr int PMAJ = PMAJ_;
+};
 
-template <typename T, int DPAD, int P, int CT_, int NBUF_, int OCC, int NW_, bool VARG, int PMAJ, bool TOP2, bool XV>
-static void launch16_kt(const AssignArgs& b, const dim3& grid, size_t lds, hipStream_t s) {
-  set_lds_attr<T, DPAD, P, CT_, NBUF_, OCC, NW_, VARG, PMAJ, TOP2, XV>();
-  if (b.D == DPAD)
-    hipLaunchKernelGGL((assign16_kernel<T, DPAD, P, CT_, NBUF_, OCC, NW_, true, VARG, PMAJ, TOP2, XV>), grid,
-                       dim3(NW_ * 64), lds, s, b);
-  else
-    hipLaunchKernelGGL((assign16_kernel<T, DPAD, P, CT_, NBUF_, OCC, NW_, false, VARG, PMAJ, TOP2, XV>), grid,
-                       dim3(NW_ * 64), lds, s, b);
+// One instantiation's launch; its LDS attribute is set once, at its first.
+template <typename T, int DPAD, typename G, typename E>
+static void launch_kernel(const AssignArgs& b, const dim3& grid, size_t lds, hipStream_t s) {
+  constexpr auto fn =
+      assign16_kernel<T, DPAD, G::P, G::CT, G::NBUF, G::OCC, G::NW, E::FULLD, E::VARG, E::PMAJ, E::TOP2, E::XV>;
+  [[maybe_unused]] static const hipError_t attr =
+      hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  hipLaunchKernelGGL(fn, grid, dim3(G::NW * 64), lds, s, b);
 }
 
 // The geometries that run the bounded E-step's TOP2 epilogue (assign_geometry routes every call
@@ -1292,30 +1127,13 @@ static void launch16_kt(const AssignArgs& b, const dim3& grid, size_t lds, hipSt
 // defaults at D = 64 / 128 / 256 spilled 400-940 VGPRs and ran 5.7x slower
 // (profiles/r4_05_hamerly_ab_top2_spills.log); the state is now the second minimum alone
 // (profiles/r4_16_top2_register_study.md), and D = 256 keeps 3 blocks at 8 waves per ring.
-template <typename T, int DPAD, int P, int OCC, int NW_>
+template <typename T, int DPAD, typename G>
 constexpr bool top2_geom() {
   if (sizeof(T) == 4 || DPAD == 32 || DPAD > 256) return true;   // (the defaults hold it, 0 spills)
-  if (DPAD == 64) return (P == 2 || P == 4) && OCC == 4 && NW_ == 4;
-  if (DPAD == 128) return (P == 2 || P == 4) && OCC == 4 && NW_ == 4;
-  if (DPAD == 256) return P == 3 && OCC == 2 && NW_ == 8;
+  if (DPAD == 64) return (G::P == 2 || G::P == 4) && G::OCC == 4 && G::NW == 4;
+  if (DPAD == 128) return (G::P == 2 || G::P == 4) && G::OCC == 4 && G::NW == 4;
+  if (DPAD == 256) return G::P == 3 && G::OCC == 2 && G::NW == 8;
   return false;
-}
-
-// With bounds (b.ub) the VARG flag says how the FULL pass of this shape ranks: by value (the
-// value-only argmin) -> the TOP2 kernel takes the exact (value, index) epilogue (XV), else the
-// packed keys; with the full pass's seed offsets (b.oseed) its labels are then the full pass's.
-template <typename T, int DPAD, int P, int CT_, int NBUF_, int OCC, int NW_, bool VARG, int PMAJ>
-static void launch16_kp(const AssignArgs& b, const dim3& grid, size_t lds, hipStream_t s) {
-  if (b.ub) {
-    if constexpr (top2_geom<T, DPAD, P, OCC, NW_>()) {
-      if constexpr (VARG && sizeof(T) == 2)
-        return launch16_kt<T, DPAD, P, CT_, NBUF_, OCC, NW_, false, PMAJ, true, true>(b, grid, lds, s);
-      else
-        return launch16_kt<T, DPAD, P, CT_, NBUF_, OCC, NW_, false, PMAJ, true, false>(b, grid, lds, s);
-    }
-    return;   // (unreachable: assign_geometry sends bounds to a top2_geom geometry)
-  }
-  launch16_kt<T, DPAD, P, CT_, NBUF_, OCC, NW_, VARG, PMAJ, false, false>(b, grid, lds, s);
 }
 
 static unsigned long long* g_timeline = nullptr;
@@ -1323,18 +1141,6 @@ static int64_t g_timeline_cap = 0;
 void set_assign_timeline(unsigned long long* buf, int64_t capacity) {
   g_timeline = buf;
   g_timeline_cap = buf ? capacity : 0;
-}
-
-template <typename T, int DPAD, int P, int CT_, int NBUF_, int OCC, int NW_, bool VARG>
-static void launch16_k(const AssignArgs& b, const dim3& grid, size_t lds, hipStream_t s) {
-  if constexpr (DPAD > 256) {   // streamed A fragments: one issue order
-    return launch16_kp<T, DPAD, P, CT_, NBUF_, OCC, NW_, VARG, 0>(b, grid, lds, s);
-  } else {
-    const int e = variant(V_ASSIGN_PMAJ);
-    const int pm = e >= 0 ? e : (sizeof(T) == 2 ? 1 : 0);
-    if (pm != 0) return launch16_kp<T, DPAD, P, CT_, NBUF_, OCC, NW_, VARG, 1>(b, grid, lds, s);
-    launch16_kp<T, DPAD, P, CT_, NBUF_, OCC, NW_, VARG, 0>(b, grid, lds, s);
-  }
 }
 
 // The persistent kernel's grid: min(groups, workgroups resident at once) -- the occupancy of
@@ -1380,17 +1186,20 @@ static hipError_t launch16_persist(const AssignArgs& b, int64_t nblk, size_t lds
 // workgroups finish after the rest weigh more on a 3.7 ms kernel) -- so from 5e7 rows up
 // (profiles/r7_01_persistent_assign.md).  V_ASSIGN_PERSIST = 0 / 1 forces it off / on wherever
 // it applies, >= 2 also caps its grid to that many workgroups (tests).
-constexpr size_t PERSIST_LDS_EXTRA = 1024;      // one old label per thread
 constexpr int PERSIST_KPAD = 1024;
 constexpr int64_t PERSIST_MIN_GROUPS = 196608;
 
-template <typename T, int DPAD, int P, int CT_ = 0, int NBUF_ = 2, int OCC = 1, int NW_ = 4>
-static hipError_t launch16_t(const AssignArgs& a, hipStream_t s) {
-  using C = Assign16Cfg<T, DPAD, P, CT_, NBUF_, NW_>;
+// A launch of geometry G (assign_geometry's Geom tag): grid, centre splits and LDS size, the persistent kernel
+// or the one-pass grid, and each run-time epilogue flag resolved once -- a constant only where its kernels are
+// built: VARG for bf16 at DPAD <= 64, PMAJ at DPAD <= 256, TOP2 on the top2_geom geometries, XV with TOP2.
+template <typename T, int DPAD, typename G>
+static hipError_t launch16(const AssignArgs& a, hipStream_t s) {
+  using C = Assign16Cfg<T, DPAD, G::P, G::CT, G::NBUF, G::NW>;
+  using L = AssignLds<C>;
+  constexpr bool BF = sizeof(T) == 2;
   if (a.Kpad % (16 * C::CT) != 0) return hipErrorInvalidValue;
-  const int cn_bytes = ((a.Kpad * 4 + 1023) / 1024) * 1024;
-  // + min/max scratch + per-point offsets + per-wave slot totals
-  const size_t lds = cn_bytes + C::NBUF * C::CHUNK_BYTES + 16 * C::NW + C::OPT_BYTES + 16 * C::NW;
+  static_assert(L::bytes(1024, true) <= 160 * 1024, "a built geometry holds 1024 centres, persistent extra included");
+  const size_t lds = L::bytes(a.Kpad, false);
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   const int64_t nblk = (a.N + C::PTS - 1) / C::PTS;
   if (nblk <= 0) return hipSuccess;
@@ -1406,29 +1215,39 @@ static hipError_t launch16_t(const AssignArgs& a, hipStream_t s) {
   // Plain full bf16 passes with caller norms at the headline geometry (the conditions of the
   // one-pass kernel's early prologue, no device row count, point-block-major issue): the
   // persistent kernel (default: see PERSIST_MIN_GROUPS).
-  if constexpr (sizeof(T) == 2 && DPAD == 128 && P == 4 && CT_ == chunk_tiles16(2, 128) && NBUF_ == 2 && OCC == 4 &&
-                NW_ == 4) {
+  if constexpr (BF && DPAD == 128 && G::P == 4 && G::CT == chunk_tiles16(2, 128) && G::NBUF == 2 && G::OCC == 4 &&
+                G::NW == 4) {
     const int pv = variant(V_ASSIGN_PERSIST);
     const int pm = variant(V_ASSIGN_PMAJ);
     const bool applies = b.xn && !b.rows && !b.oseed && !b.split_keys && !b.n_dev && !b.ub && b.epi_prefetch &&
                          b.early_prologue && b.D == DPAD && (pm < 0 || pm == 1);
     const bool dflt = b.Kpad == PERSIST_KPAD && nblk >= PERSIST_MIN_GROUPS;
-    if (applies && lds + PERSIST_LDS_EXTRA <= 160 * 1024 && (pv >= 0 ? pv != 0 : dflt))
-      return launch16_persist<DPAD, P, OCC, 1>(b, nblk, lds + PERSIST_LDS_EXTRA, pv >= 2 ? pv : 0, s);
+    const size_t plds = L::bytes(a.Kpad, true);   // + one old label per thread
+    if (applies && plds <= 160 * 1024 && (pv >= 0 ? pv != 0 : dflt))
+      return launch16_persist<DPAD, G::P, G::OCC, 1>(b, nblk, plds, pv >= 2 ? pv : 0, s);
   }
-  bool varg = false;
-  constexpr bool VARG_OK = sizeof(T) == 2 && DPAD <= 64;   // D=128: -12 % at K=1024, -4 % at 2048 (r3_11)
+  constexpr bool VARG_OK = BF && DPAD <= 64;   // D=128: -12 % at K=1024, -4 % at 2048 (r3_11)
+  constexpr bool PMAJ_OK = DPAD <= 256;        // (wider: streamed A fragments, one issue order)
+  bool varg = false, pmaj = false;
   if constexpr (VARG_OK) {
     const int e = variant(V_ASSIGN_VARG);
-    // (with bounds: whether the full pass would, see launch16_kp)
     varg = e >= 0 ? e != 0 : a.Kpad >= (DPAD == 64 ? 2048 : 1024);
   }
-  if constexpr (VARG_OK) {
-    if (varg) launch16_k<T, DPAD, P, CT_, NBUF_, OCC, NW_, true>(b, grid, lds, s);
-    else launch16_k<T, DPAD, P, CT_, NBUF_, OCC, NW_, false>(b, grid, lds, s);
-  } else {
-    launch16_k<T, DPAD, P, CT_, NBUF_, OCC, NW_, false>(b, grid, lds, s);
+  if constexpr (PMAJ_OK) {
+    const int e = variant(V_ASSIGN_PMAJ);
+    pmaj = (e >= 0 ? e : (BF ? 1 : 0)) != 0;
   }
+  for_flag(b.D == DPAD, [&](auto fd) { return for_flag(varg, [&](auto vg) { return for_flag(pmaj, [&](auto pm) {
+    constexpr bool FULLD = decltype(fd)::value, VARG = VARG_OK && decltype(vg)::value;
+    constexpr int PMAJ = PMAJ_OK && decltype(pm)::value ? 1 : 0;
+    if (!b.ub) launch_kernel<T, DPAD, G, Epi<VARG, PMAJ, false, false, FULLD>>(b, grid, lds, s);
+    // With bounds (b.ub) the VARG flag says how the FULL pass of this shape ranks: by value (the
+    // value-only argmin) -> the TOP2 kernel takes the exact (value, index) epilogue (XV), else the
+    // packed keys; with the full pass's seed offsets (b.oseed) its labels are then the full pass's.
+    else if constexpr (top2_geom<T, DPAD, G>())   // (else unreachable: assign_geometry sends bounds to one)
+      launch_kernel<T, DPAD, G, Epi<false, PMAJ, true, VARG, FULLD>>(b, grid, lds, s);
+    return 0;
+  }); }); });
   if (splits > 1)
     hipLaunchKernelGGL(split_finish_kernel, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, s, b);
   return hipGetLastError();
@@ -1550,10 +1369,8 @@ hipError_t launch_assign16(int dtype, int dpad, const AssignArgs& a, hipStream_t
   return (hipError_t)for_width(dtype, dpad, [&](auto t, auto w) {
     using T = typename decltype(t)::type;
     constexpr int DPAD = decltype(w)::value;
-    return assign_geometry<T, DPAD>(a.Kpad, a.ub != nullptr, [&](auto g) {
-      using G = decltype(g);
-      return launch16_t<T, DPAD, G::P, G::CT, G::NBUF, G::OCC, G::NW>(a, s);
-    });
+    return assign_geometry<T, DPAD>(a.Kpad, a.ub != nullptr,
+                                    [&](auto g) { return launch16<T, DPAD, decltype(g)>(a, s); });
   });
 }
 

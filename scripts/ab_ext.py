@@ -11,6 +11,7 @@ inputs in interleaved rounds, so box-to-box clock differences cancel.
   python scripts/ab_ext.py build HEAD~1            # prints the module path
   python scripts/ab_ext.py run scripts/abbin/_C_ab_<sha>.so --n 20000000 --d 128 --k 1024
   python scripts/ab_ext.py run scripts/abbin/_C_ab_<sha>.so --what rows   # the row kernels, bit for bit
+  python scripts/ab_ext.py run scripts/abbin/_C_ab_<sha>.so --what assign --mode bounded   # an assign mode, bit for bit
 """
 from __future__ import annotations
 
@@ -274,6 +275,177 @@ def cmd_rows(mods, a) -> int:
     return 0 if all(k["outputs_equal_head"] for k in out["kernels"].values()) else 1
 
 
+ASSIGN_MODES = ("plain", "noxn", "split", "gathered", "bounded", "persist")
+
+
+def _assign_cases(mode):
+    """``--what assign --mode``: the small cases of a mode, ``(dtype, D, chunks, outlier, variants)``.
+    ``chunks``: K in chunks of centres (1, or 17: an odd count, so the persistent ring's slot
+    parity flips, and a last key segment of fewer than 16 tiles); ``outlier``: row 3 scaled x64
+    (its workgroup takes per-point seed offsets); ``variants``: A/B switches set on each module
+    (upper case) and options of the case (``oseed``: pass, or withhold, the full pass's seed offsets).
+    Across the modes every built width, a D below its padded width, both offset modes and
+    every assign switch occur at least once."""
+    bf, f32 = "bf16", "f32"
+    if mode == "plain":
+        for dt, ds in ((bf, (32, 64, 128, 256, 384, 512, 768, 1024)), (f32, (32, 128, 512, 1024))):
+            for D in ds:
+                yield dt, D, 1, False, {}
+                yield dt, D, 17, True, {}
+        yield bf, 104, 17, False, {}           # (D below the padded width: the column-checked loads)
+        yield f32, 100, 17, True, {}
+        for v in (0, 1):
+            yield bf, 64, 17, bool(v), {"ASSIGN_VARG": v}
+            yield bf, 128, 17, bool(v), {"ASSIGN_PMAJ": v}
+            yield f32, 128, 17, False, {"ASSIGN_PMAJ": v}
+        yield bf, 128, 34, False, {"ASSIGN_GEOM": 1}    # (32 KiB chunks: 17 of them)
+        yield bf, 128, 17, True, {"ASSIGN_GEOM": 2}
+        yield bf, 256, 17, False, {"ASSIGN_GEOM": 1}
+    elif mode == "noxn":
+        for dt, D, o in ((bf, 128, False), (bf, 64, True), (bf, 512, False), (f32, 128, False), (f32, 100, True)):
+            yield dt, D, 17, o, {}
+    elif mode == "split":
+        for dt, D, o in ((bf, 128, False), (bf, 128, True), (bf, 104, True), (bf, 512, False), (f32, 128, False)):
+            yield dt, D, 17, o, {}
+        yield bf, 64, 17, False, {"ASSIGN_VARG": 1}
+    elif mode == "gathered":
+        for dt, D, o in ((bf, 128, False), (bf, 256, True), (bf, 768, False), (f32, 32, False)):
+            yield dt, D, 17, o, {}
+        yield bf, 64, 17, False, {"ASSIGN_VARG": 1, "oseed": True}    # (the value-only argmin under per-row offsets)
+        yield bf, 128, 17, False, {"oseed": True}
+    elif mode == "bounded":
+        for dt, D, o in ((bf, 32, False), (bf, 128, False), (bf, 128, True), (bf, 256, True), (bf, 384, False),
+                         (f32, 128, False)):
+            yield dt, D, 17, o, {}
+        for v in (0, 1):                       # (1: the full pass ranks by value, so the exact bf16 epilogue)
+            yield bf, 64, 17, bool(v), {"ASSIGN_VARG": v}
+        yield bf, 128, 17, False, {"ASSIGN_TOP2_GEOM": 0}
+        for o in (False, True):                # (no seed offsets: the TOP2 epilogues under the shared / per-point offsets)
+            yield bf, 128, 17, o, {"oseed": False}
+            yield bf, 64, 17, o, {"ASSIGN_VARG": 1, "oseed": False}
+    elif mode == "persist":
+        for chunks, o in ((1, False), (17, False), (17, True)):
+            yield bf, 128, chunks, o, {"ASSIGN_PERSIST": 5}
+
+
+def _assign_prep(torch, m, mode, dt, X, Cen, code, dpad, K, opts):
+    """One module's inputs and outputs of an assign in ``mode`` on rows X: ``(run, outputs)``; its own
+    pack, norms, scratch and outputs, and the same input state before every ``run()``."""
+    dev, n = X.device, X.shape[0]
+    f32, i32, i64 = torch.float32, torch.int32, torch.int64
+    kpad = m.assign_kpad(code, dpad, K)
+    pack = torch.zeros(kpad * dpad, dtype=dt, device=dev)
+    cn = torch.zeros(m.assign_cn_len(kpad), dtype=f32, device=dev)
+    m.finalize(0, None, Cen, None, None, None, pack, cn, None, None, dpad, kpad)
+    xn = torch.empty(n, dtype=f32, device=dev)
+    m.row_sqnorm(X, xn)
+    lab, mind = torch.empty(n, dtype=i32, device=dev), torch.empty(n, dtype=f32, device=dev)
+    slots = torch.empty(m.NSLOT * m.SLOT_STRIDE, dtype=torch.float64, device=dev)
+    ub, lb = torch.empty(n, dtype=f32, device=dev), torch.empty(n, dtype=f32, device=dev)
+    args, kw, outs = [X, pack, cn, xn, lab, mind, slots, kpad, dpad, True], {}, [lab, mind, slots]
+    if mode == "noxn":
+        args[3], args[5], outs = None, None, [lab, slots]
+    if mode == "split":
+        kw["keys"] = torch.full((n,), -1, dtype=i64, device=dev)
+        outs.append(kw["keys"])
+    if mode == "gathered":     # a permutation with repeats, and a device count short of its length
+        g = torch.Generator(device=dev).manual_seed(n)
+        rows = torch.randperm(n, generator=g, device=dev)
+        rows[1::5] = rows[0::5][: rows[1::5].numel()]
+        kw.update(rows=rows, count=torch.tensor([n - 5], dtype=i64, device=dev))
+    if mode == "bounded":      # two rows of three, outputs at their X rows, the full pass's seed offsets
+        kw.update(rows=torch.arange(n, device=dev)[torch.arange(n, device=dev) % 3 != 0].contiguous(), ub=ub, lb=lb,
+                  scatter=True)
+        outs += [ub, lb]
+    if dt == torch.bfloat16 and opts.get("oseed", mode == "bounded"):
+        kw["oseed"] = torch.empty(n, dtype=f32, device=dev)
+        m.seed_offsets(xn, kw["oseed"], m.assign_block_rows(code, dpad, kpad))
+
+    def run(reset=True):
+        if reset:
+            lab.fill_(7)
+            mind.fill_(-1.0)
+            slots.zero_()
+            ub.zero_()
+            lb.zero_()
+        m.assign(*args, **kw)
+    return run, outs
+
+
+def cmd_assign_modes(mods, a) -> int:
+    """``--what assign --mode M``: every output of every module (labels, mind, ub / lb, the slot
+    words, the keys scratch) against the head's, bit for bit -- on the mode's small cases, or,
+    with ``--n`` / ``--d`` / ``--k``, on that one shape, timed in interleaved rounds."""
+    import torch
+
+    from mikmeans.ops import native
+
+    dev = torch.device("cuda")
+    ints = {torch.float32: torch.int32, torch.float64: torch.int64}
+    timed = a.n is not None or a.d is not None or a.k is not None
+    if timed:
+        cases = [(a.dtype, a.d or 128, None, False, {"ASSIGN_PERSIST": 1} if a.mode == "persist" else {})]
+    else:
+        cases = list(_assign_cases(a.mode))
+    differ, res = [], {"what": "assign", "mode": a.mode, "cases": len(cases)}
+    for dts, D, chunks, outlier, variants in cases:
+        opts = {k: v for k, v in variants.items() if k.islower()}
+        variants = {k: v for k, v in variants.items() if not k.islower()}
+        dt = torch.bfloat16 if dts == "bf16" else torch.float32
+        code, v = native.dtype_code(dt), (8 if dts == "bf16" else 4)
+        Dp = -(-D // v) * v
+        dpad = native.dpad_for(Dp, dt)
+        tag = f"{dts} D={D} chunks={chunks} outlier={int(outlier)} {variants} {opts}"
+        runs, snap = {}, {}
+        for name, m in mods.items():
+            names = m.variant_names()
+            for kname, kv in variants.items():
+                m.set_variant(names.index(kname), kv)
+            # (the chunk and the workgroup's rows under the case's switches, from the module itself)
+            K = (a.k or 1024) if timed else chunks * m.assign_kpad(code, dpad, 1)
+            kpad = m.assign_kpad(code, dpad, K)
+            groups = 11 if a.mode == "persist" else 3
+            n = (a.n or 20_000_000) if timed else groups * m.assign_block_rows(code, dpad, kpad) + 17
+            g = torch.Generator(device=dev).manual_seed(D + K)
+            X = torch.zeros((n, Dp), dtype=dt, device=dev)
+            X[:, :D] = (torch.randn((n, D), generator=g, device=dev) * 3).to(dt)
+            if outlier:
+                X[3] *= 64
+            Cen = torch.zeros((K, Dp), dtype=torch.float32, device=dev)
+            Cen[:, :D] = torch.randn((K, D), generator=g, device=dev) * 3
+            runs[name], outs = _assign_prep(torch, m, a.mode, dt, X, Cen, code, dpad, K, opts)
+            runs[name]()
+            torch.cuda.synchronize()
+            snap[name] = [o.view(ints.get(o.dtype, o.dtype)).clone() for o in outs]
+            if not timed:
+                for kname in variants:
+                    m.set_variant(names.index(kname), -1)
+                del X, Cen
+        for name in mods:
+            if not all(torch.equal(x, y) for x, y in zip(snap[name], snap["head"])):
+                differ.append(f"{name}: {tag}")
+        # (a guard on the comparison itself: the head's labels are no constant)
+        res["min_distinct_labels"] = min(res.get("min_distinct_labels", 1 << 30), int(snap["head"][0].unique().numel()))
+        if timed:
+            ts = {name: [] for name in mods}
+            for _ in range(a.rounds):
+                for name in mods:
+                    ts[name] += _timed(lambda r=runs[name]: r(False), a.reps)   # (the launch alone)
+            res.update(n=n, d=D, k=K, dtype=dts, variants={})
+            for name, t in ts.items():
+                rmed = [statistics.median(t[i: i + a.reps]) for i in range(0, len(t), a.reps)]
+                res["variants"][name] = {"median_ms": round(statistics.median(t), 4), "min_ms": round(min(t), 4),
+                                         "round_median_spread_ms": round(max(rmed) - min(rmed), 4),
+                                         "vs_head": round(statistics.median(ts["head"]) / statistics.median(t), 4)}
+        del runs, snap
+    res.update(outputs_equal_head=not differ, differ=differ)
+    print(json.dumps(res), flush=True)
+    if res["min_distinct_labels"] <= 1:
+        print("every label of a case is the same: the comparison says nothing", file=sys.stderr)
+        return 1
+    return 0 if not differ else 1
+
+
 def cmd_run(a) -> int:
     import torch
 
@@ -287,7 +459,12 @@ def cmd_run(a) -> int:
     for p in a.modules:
         meta = Path(p).with_suffix(".json")
         tag = json.loads(meta.read_text())["ref"] if meta.exists() else Path(p).stem
+        while tag in mods:   # (the same module twice: an A/A control)
+            tag += "'"
         mods[tag] = load_module(p)
+    if a.what == "assign" and a.mode is not None:
+        return cmd_assign_modes(mods, a)
+    a.n, a.d, a.k, a.mode = a.n or 20_000_000, a.d or 128, a.k or 1024, a.mode or "plain"
     if a.what == "rows":   # its own shapes, many and small (--n / --d / --k / --dtype do not apply)
         return cmd_rows(mods, a)
     dt = torch.bfloat16 if a.dtype == "bf16" else torch.float32
@@ -474,21 +651,29 @@ def main(argv=None) -> int:
     b.add_argument("ref")
     r = sub.add_parser("run")
     r.add_argument("modules", nargs="+")
-    r.add_argument("--n", type=int, default=20_000_000)
-    r.add_argument("--d", type=int, default=128)
-    r.add_argument("--k", type=int, default=1024)
+    r.add_argument("--n", type=int, default=None, help="rows (default 20000000)")
+    r.add_argument("--d", type=int, default=None, help="features (default 128)")
+    r.add_argument("--k", type=int, default=None, help="centres (default 1024)")
     r.add_argument("--dtype", default="bf16")
     r.add_argument("--rounds", type=int, default=5)
     r.add_argument("--reps", type=int, default=5)
     r.add_argument("--what", default="assign", choices=["assign", "update", "blobs", "colstats", "rownorms",
                                                         "transform", "topk", "ivf_scan", "ivf_range", "rows"])
-    r.add_argument("--mode", default="plain", choices=["plain", "weighted", "clamp", "resid", "gather", "delta"],
-                   help="update: the pass (each reaches another build of the M-step kernels)")
+    r.add_argument("--mode", default=None,
+                   choices=["plain", "weighted", "clamp", "resid", "gather", "delta", *ASSIGN_MODES[1:]],
+                   help="update: the pass (each reaches another build of the M-step kernels; default plain).  "
+                        "assign: every output against the head's bit for bit, on the mode's small cases "
+                        f"({', '.join(ASSIGN_MODES)}) or, with --n / --d / --k, timed on that shape; "
+                        "without --mode the plain full pass is timed")
     r.add_argument("--m", type=int, default=8,
                    help="topk / ivf_scan: list length; ivf_range: the radius is the m-th nearest row's distance")
     r.add_argument("--nq", type=int, default=10_000, help="ivf_scan / ivf_range: queries (the first rows)")
     r.add_argument("--nprobe", type=int, default=16, help="ivf_scan / ivf_range: lists probed per query")
     a = ap.parse_args(argv)
+    if a.cmd == "run" and a.mode is not None:
+        modes = {"assign": ASSIGN_MODES, "update": ("plain", "weighted", "clamp", "resid", "gather", "delta")}
+        if a.mode not in modes.get(a.what, ()):
+            ap.error(f"--what {a.what} takes no --mode {a.mode}")
     if a.cmd == "build":
         cmd_build(a.ref)
         return 0

@@ -533,13 +533,24 @@ def test_predict_reuses_pack_until_centres_change(native):
     assert torch.equal(km.predict(X), l1) and km._pack_cache[0] is km.cluster_centers_
 
 
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
-@pytest.mark.parametrize("n,d,k", [(1, 128, 1024), (1000, 128, 1024), (16384, 64, 4096), (3000, 256, 512),
-                                   (70000, 32, 300), (5000, 128, 70)])
-def test_assign_centre_split_small_batches(native, dtype, n, d, k):
+_SPLIT_SHAPES = [(1, 128, 1024), (1000, 128, 1024), (16384, 64, 4096), (3000, 256, 512), (70000, 32, 300),
+                 (5000, 128, 70)]
+
+
+# (the ids of the shape x dtype grid as two stacked parametrize marks gave them, plus one case)
+@pytest.mark.parametrize(
+    "n,d,k,dtype,outlier",
+    [pytest.param(n, d, k, dt, False, id=f"{n}-{d}-{k}-dtype{i}")
+     for i, dt in enumerate([torch.bfloat16, torch.float32]) for n, d, k in _SPLIT_SHAPES]
+    + [pytest.param(1000, 128, 1024, torch.bfloat16, True, id="1000-128-1024-bf16-outlier")])
+def test_assign_centre_split_small_batches(native, dtype, n, d, k, outlier):
     """Small batches split the centre range over workgroups; labels, distances and the
-    inertia / changed counters equal the one-pass kernel's, calls reuse the scratch."""
+    inertia / changed counters equal the one-pass kernel's, calls reuse the scratch.
+    ``outlier``: row 3 scaled x64, so its workgroup takes per-point seed offsets and the split
+    parks a per-row offset for split_finish (compared with the one-pass call alone)."""
     X = _points(n, d, dtype, seed=n + k)
+    if outlier:
+        X[3] *= 64
     C = _points(k, d, torch.float32, seed=k + 11)
     Xp = ops.pad_columns(X.to(DEV))
     pk = ops.pack_centers(C.to(DEV), Xp.shape[1], Xp.dtype, DEV)
@@ -562,7 +573,8 @@ def test_assign_centre_split_small_batches(native, dtype, n, d, k):
         assert torch.equal(mind, res[0][1])
         assert changed == res[0][3] == float((res[0][0] != 7).sum())
         assert inert == pytest.approx(res[0][2], rel=1e-6)
-    _check_assign(X, C, res[1][0], res[1][1], rel=2e-5 if dtype == torch.float32 else 3e-5)
+    if not outlier:
+        _check_assign(X, C, res[1][0], res[1][1], rel=2e-5 if dtype == torch.float32 else 3e-5)
 
 
 @pytest.mark.parametrize("dtype", ["bfloat16", "float32"])
