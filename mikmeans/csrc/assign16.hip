@@ -196,8 +196,16 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
   // instruction per 4 blocks instead of one per block (the prologue's vector-memory issue is
   // what takes its time, profiles/r5_45_assign_prologue_study.md); lanes past the last block
   // repeat it (harmless to the max / min)
+  // ... and with the per-fit table (a.gstats) the group's max / min |x|^2 come by scalar load: no reduction,
+  // no exchange and no barrier stand between the norms' landing and the chunk loop
+  constexpr bool TAB_OK = EARLY_OK && DPAD == 128 && C::PTS == GSTATS_ROWS && !VARG && !TOP2;   // (the headline geometry)
+  const bool tab = TAB_OK && early && a.gstats;
+  float gmax = 0.f, gmin = 3.0e38f;
   float xg[EJ];
   if (early) {
+    if constexpr (TAB_OK) {
+      if (tab) gstats_load(a.gstats, blockIdx.x, gmax, gmin);
+    }
     cn_issue<C>(rN, cn_lds, cn_bytes, wid, loff);
 #pragma unroll
     for (int j = 0; j < EJ; ++j) xg[j] = a.xn[row_of(4 * j + g < C::P ? 4 * j + g : C::P - 1)];
@@ -298,6 +306,11 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
         for (int p = 0; p < C::P; ++p) opt[L.row(wid, r) + p] = osr[p];
       }
      } else {
+      float mnw = 3.0e38f;
+      if (tab) {   // the table's pair is the reduction's result; this wave's own |c|^2 pieces landed (its wait above)
+        off = gmax;
+        mnw = gmin;
+      } else {
       float m = 0.f, mn = 3.0e38f;
       if (early) {   // (one norm per lane and 4 blocks: reduce over the whole wave)
 #pragma unroll
@@ -321,16 +334,17 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
       // prologue's fragments and first chunk stay in flight (__syncthreads drains vmcnt)
       wait_lgkm0();
       raw_barrier();
-      // The seed rule; it stands again in assign16_persist_kernel, line for line but for the thread id and
-      // the parking -- change both (as a function it moved every bf16 kernel's registers, profiles/r14_01).
-      float mnw = 3.0e38f;
 #pragma unroll
       for (int w = 0; w < C::NW; ++w) { off = fmaxf(off, red[2 * w]); mnw = fminf(mnw, red[2 * w + 1]); }
+      }
+      // The seed rule; it stands again in assign16_persist_kernel, line for line but for the thread id and
+      // the parking -- change both (as a function it moved every bf16 kernel's registers, profiles/r14_01).
       ppo = __builtin_amdgcn_readfirstlane((int)(off > 4.f * mnw)) != 0;
       if (!ppo) {
         off = seed_scale(off);
         off = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(off)));
-        for (int k = threadIdx.x; k < a.Kpad; k += C::NW * 64) ((float*)cn_lds)[k] += off;
+        if (tab) cn_fold_own<C>(cn_lds, cn_bytes, wid, lane, off);
+        else for (int k = threadIdx.x; k < a.Kpad; k += C::NW * 64) ((float*)cn_lds)[k] += off;
       } else {
         off = 0.f;
         if (early) {
@@ -704,8 +718,12 @@ __global__ __launch_bounds__(NW_ * 64, OCC) void assign16_kernel(AssignArgs a) {
 // it as in the one-pass kernel (adding the offset per tile instead, on a pristine copy, cost
 // 4 VALU a tile: the SIMDs are bound by MFMA + VALU issue, not by waiting waves).
 // vmcnt order per wave and group: [chunk 0] [old labels] [norms] [P*NQ fragments] [epilogue
-// stores, slot atomics] [|c|^2]; the epilogue's wait for the old labels is counted on the norms
+// stores, slot atomics] [|c|^2] [thread 0: the group counter's atomic, behind chunk 0's barrier]
+// [chunk 1] ...; the epilogue's wait for the old labels is counted on the norms
 // and fragments (the only younger operations that are issued unconditionally).
+// With the per-fit group statistics (AssignArgs::gstats) the group top has no reduction, no exchange
+// and no barrier: the group's max / min |x|^2 arrive by scalar load, issued where the group became
+// known, and each wave folds the offset into the |c|^2 pieces it sent itself (assign_step.h cn_fold_own).
 // A kernel of its own, not a flag of assign16_kernel: the scope is one epilogue of that
 // kernel's five, and tests/test_isa_guard.py indexes assign16_kernel's template arguments.
 // Group counters of the persistent kernel, {next group - G, workgroups done}, zero between
@@ -781,6 +799,14 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
   auto ld128 = [](u32x4& d, uint32_t vo, const void* base) {
     asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(d) : "v"(vo), "s"(base) : "memory");
   };
+  // The group counter's returning atomic, inline asm tied to its register for the same reason: as a compiler-visible
+  // atomicAdd on a uniform address it became a wave-aggregated atomic whose result a v_readfirstlane read at once,
+  // behind a vmcnt(0) -- one exposed round trip per group wherever it stood.  Thread 0 calls it; a chunk head's
+  // vmcnt(0) retires it before the last chunk's head reads `d` (tests/test_isa_persist_counter.py reads the code
+  // object: one register at every site, untouched until that wait).
+  auto fetch_add1 = [](unsigned& d, unsigned* counter) {
+    asm volatile("global_atomic_add %0, %1, %2, %3 sc0" : "+v"(d) : "v"(0u), "v"(1u), "s"(counter) : "memory");
+  };
   auto blds4 = [](__amdgpu_buffer_rsrc_t rs, MK_LDS void* lds_base, uint32_t voff) {   // lane i -> lds_base + 4 i
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, lds_base, 4, voff, 0, 0, 0);
   };
@@ -823,6 +849,12 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
   // starts from a fresh copy (4 KiB at K = 1024; a pristine second copy does not fit the LDS
   // of four workgroups)
   auto issue_cn = [&]() { cn_issue<C>(make_rsrc(a.cn, (uint32_t)a.Kpad * 4u), cn_lds, cn_bytes, wid, loff); };
+  // With the per-fit table (a.gstats) a group's max / min |x|^2 is a scalar load, issued where the group
+  // becomes known -- here, then at the last chunk's head for the next -- and read at the group's top.
+  static_assert(C::PTS == GSTATS_ROWS, "the table's groups are this kernel's");
+  const bool tab = a.gstats != nullptr;
+  float gmax = 0.f, gmin = 3.0e38f;
+  if (tab) gstats_load(a.gstats, grp, gmax, gmin);
   issue_cn();
   issue_chunk(0, 0);
   load_group(grp);
@@ -849,6 +881,13 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
       fetched = 0u;
       const int tln = ttid & 63, tr = ttid & 15, tg = tln >> 4;
       const ShflLaundered sh{tln};
+      float mnw = 3.0e38f;
+      if (tab) {
+        // the table's pair is the reduction's result: no exchange, no barrier (the group-end barrier already
+        // stands between every wave's last read of |c|^2 and its re-send; opt is each wave's own)
+        off = gmax;
+        mnw = gmin;
+      } else {
       float m = 0.f, mn = 3.0e38f;
 #pragma unroll
       for (int j = 0; j < EJ; ++j) { m = fmaxf(m, exn[j]); mn = fminf(mn, exn[j]); }
@@ -867,17 +906,22 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
       wait_lgkm0();
       raw_barrier();
       // (every wave's |c|^2 pieces landed before the barrier above)
-      // The seed rule; it stands again in assign16_kernel, line for line but for thread id and parking: change both.
-      float mnw = 3.0e38f;
 #pragma unroll
       for (int w = 0; w < C::NW; ++w) { off = fmaxf(off, red[2 * w]); mnw = fminf(mnw, red[2 * w + 1]); }
+      }
+      // The seed rule; it stands again in assign16_kernel, line for line but for thread id and parking: change both.
       ppo = __builtin_amdgcn_readfirstlane((int)(off > 4.f * mnw)) != 0;
-      // the next group: one returning atomic per group, a whole chunk loop ahead of its use
-      if (ttid == 0) fetched = atomicAdd(ctr, 1u);
+      // (a one-chunk pass: its only chunk head consumes the next group, so the fetch goes out here and is
+      // waited for at once -- on the way into either loop copy the compiler may move `fetched`)
+      if (ncl < 2) {
+        if (ttid == 0) fetch_add1(fetched, ctr);
+        wait_vmcnt<0>();
+      }
       if (!ppo) {
         off = seed_scale(off);
         off = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(off)));
-        for (int kk = ttid; kk < a.Kpad; kk += C::NW * 64) ((float*)cn_lds)[kk] += off;
+        if (tab) cn_fold_own<C>(cn_lds, cn_bytes, wid, tln, off);
+        else for (int kk = ttid; kk < a.Kpad; kk += C::NW * 64) ((float*)cn_lds)[kk] += off;
       } else {
         off = 0.f;
 #pragma unroll
@@ -904,10 +948,17 @@ __global__ __launch_bounds__(256, OCC) void assign16_persist_kernel(AssignArgs a
       wait_lgkm0();
       raw_barrier();  // RAW for chunk c, WAR for the slot refilled next (read at c-1)
       if constexpr (!decltype(last_tag)::value) {
+        // the next group: one returning atomic per group, behind chunk 0's barrier -- chunk 1's wait retires it
+        // with that chunk's own pieces (same round trip), and the last chunk's head consumes it.  (Ahead of
+        // chunk 0's head it was the only operation that head waited for: a round trip for the whole workgroup.)
+        if (c == 0) {
+          if (fresh_tid() == 0) fetch_add1(fetched, ctr);
+        }
         issue_chunk(c + 1, (s0 + c + 1) & 1);
       } else {
         nxt = __builtin_amdgcn_readfirstlane(*nxt_lds);
         has_next = nxt < ngroups;
+        if (tab) gstats_load(a.gstats, nxt < ngroups ? nxt : ngroups - 1, gmax, gmin);
         if (has_next) issue_chunk(0, (s0 + c + 1) & 1);
         const int tid = fresh_tid();
         const __amdgpu_buffer_rsrc_t rLo = make_rsrc(a.labels + (int64_t)grp * C::PTS, (uint32_t)nvc * 4u);

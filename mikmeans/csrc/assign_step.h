@@ -87,6 +87,28 @@ __device__ __forceinline__ void cn_issue(__amdgpu_buffer_rsrc_t rN, char* cn_lds
 // The bf16 seed scale, x (1 + 2^-12); the rule that uses it stays spelled at its two sites (see there)
 __device__ __forceinline__ float seed_scale(float x) { return __builtin_fmaf(x, 2.44140625e-04f, x); }
 
+// With the per-fit table (AssignArgs::gstats) a group's (max, min) |x|^2 is a scalar load -- gi is wave-uniform
+// and the table read-only for the launch: the constant address space makes it SMEM, the pair lands in SGPRs.
+__device__ __forceinline__ void gstats_load(const float* table, int64_t gi, float& mx, float& mn) {
+  typedef float pair_t __attribute__((ext_vector_type(2)));
+  const pair_t v = ((const __attribute__((address_space(4))) pair_t*)table)[gi];
+  mx = v[0];
+  mn = v[1];
+}
+// ... and each wave folds the seed offset into the |c|^2 pieces it sent itself (cn_issue: wid, wid + NW, ...;
+// lane i 16 B of each), after its own vmcnt wait: no other wave's data is touched, so no barrier stands before
+// it -- the first chunk's barrier publishes the folded copy with the chunk.
+template <typename C>
+__device__ __forceinline__ void cn_fold_own(char* cn_lds, int cn_bytes, int wid, int lane, float off) {
+  for (int pc = wid; pc < cn_bytes / 1024; pc += C::NW) {
+    f32x4* p = (f32x4*)(cn_lds + pc * 1024 + lane * 16);
+    f32x4 v = *p;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] += off;
+    *p = v;
+  }
+}
+
 // The tile step.  Every lane calls these, once per 16-centre tile, in this order.
 // Seed the P accumulators with the tile's |c|^2 (ci: cn_lds rows 4 g .. 4 g + 3 of the tile).  PPO 1, or 2
 // with ppo set at run time: plus the points' offsets (opt_row: the lane's row of opt, published by a barrier).

@@ -101,7 +101,8 @@ void assign(const Tensor& X, const Tensor& pack, const Tensor& cn, const c10::op
             const c10::optional<Tensor>& slots, int64_t Kpad, int64_t dpad, bool track_changed,
             const c10::optional<Tensor>& keys, const c10::optional<Tensor>& rows,
             const c10::optional<Tensor>& ub, const c10::optional<Tensor>& lb, bool scatter,
-            const c10::optional<Tensor>& count, const c10::optional<Tensor>& oseed) {
+            const c10::optional<Tensor>& count, const c10::optional<Tensor>& oseed,
+            const c10::optional<Tensor>& gstats) {
   const int dt = dtype_of(X);
   const int64_t ldx = check_points_dpad(X, dt, dpad);
   // gathered batch: N logical rows, row i = X[rows[i]] (indices from sample_index: in range
@@ -163,6 +164,12 @@ void assign(const Tensor& X, const Tensor& pack, const Tensor& cn, const c10::op
     TORCH_CHECK(dt == mk::DT_BF16, "mikmeans: seed offsets are the bf16 keys'");
     check_f32(*oseed, "oseed", X.size(0));
     a.oseed = oseed->data_ptr<float>();
+  }
+  if (gstats.has_value() && gstats->defined()) {   // the rows' per-group (max, min) |x|^2, from group_norm_stats(xn)
+    TORCH_CHECK(xn.has_value() && !gathered, "mikmeans: group statistics are a plain full pass's, with its xn");
+    check_f32(*gstats, "gstats", 2 * ((N + mk::GSTATS_ROWS - 1) / mk::GSTATS_ROWS));
+    TORCH_CHECK((uintptr_t)gstats->data_ptr() % 8 == 0, "mikmeans: gstats must be 8-byte aligned");
+    a.gstats = gstats->data_ptr<float>();
   }
   hip_check(mk::launch_assign16(dt, (int)dpad, a, stream()), "assign");
 }
@@ -1098,6 +1105,17 @@ void tighten(const Tensor& X, int64_t D, const Tensor& labels, const Tensor& C, 
             "tighten");
 }
 
+// out[2 g], out[2 g + 1] = (max, min) of xn over the assign's 256-row group g (AssignArgs::gstats)
+void group_norm_stats(const Tensor& xn, const Tensor& out, int64_t row0) {
+  const int64_t n = xn.numel();
+  check_f32(xn, "xn", n);
+  check_f32(out, "out", 2 * ((n + mk::GSTATS_ROWS - 1) / mk::GSTATS_ROWS));
+  TORCH_CHECK(row0 >= 0 && row0 % mk::GSTATS_ROWS == 0, "mikmeans: row0 must lie on the ", mk::GSTATS_ROWS,
+              "-row group grid (got ", row0, ")");
+  hip_check(mk::launch_group_norm_stats(xn.data_ptr<float>(), n, row0, out.data_ptr<float>(), stream()),
+            "group_norm_stats");
+}
+
 // oseed = the full assign's per-row seed offsets (bf16 keys) for rows with norms xn
 void seed_offsets(const Tensor& xn, const Tensor& oseed, int64_t block_rows) {
   const int64_t n = xn.numel();
@@ -1189,7 +1207,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("xn"), py::arg("labels"), py::arg("mind"), py::arg("slots"), py::arg("Kpad"), py::arg("dpad"),
         py::arg("track_changed"), py::arg("keys") = py::none(), py::arg("rows") = py::none(),
         py::arg("ub") = py::none(), py::arg("lb") = py::none(), py::arg("scatter") = false,
-        py::arg("count") = py::none(), py::arg("oseed") = py::none());
+        py::arg("count") = py::none(), py::arg("oseed") = py::none(), py::arg("gstats") = py::none());
+  m.def("group_norm_stats", &group_norm_stats, "per-group (max, min) row norms: the assign's seed statistics, once per fit",
+        py::arg("xn"), py::arg("out"), py::arg("row0") = 0);
+  m.attr("GSTATS_ROWS") = (int)mk::GSTATS_ROWS;
   m.def("seed_offsets", &seed_offsets, "the full assign's per-row bf16 seed offsets (bounded E-step)");
   m.def("assign_block_rows", [](int64_t dt, int64_t dpad, int64_t kpad) {
     return mk::assign16_block_rows((int)dt, (int)dpad, (int)kpad);

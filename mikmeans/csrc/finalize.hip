@@ -126,6 +126,44 @@ hipError_t launch_row_sqnorm(int dtype, const void* X, int64_t N, int D, int64_t
   });
 }
 
+// The assign's per-group seed statistics (kernels.h AssignArgs::gstats): out[2 g], out[2 g + 1] = max, min of
+// xn over group g's rows, folded as the assign kernels fold them -- fmaxf from 0, fminf from 3e38 -- so an
+// entry is bitwise what a workgroup's own reduction gives.  A wave per group, lane i the rows i, i + 64, ...;
+// a lane past the last group's valid rows repeats the last valid one (the kernels' clamp).
+__global__ __launch_bounds__(256) void group_norm_stats_kernel(const float* __restrict__ xn, int64_t n,
+                                                               int64_t ngroups, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * 4;
+  for (int64_t gi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); gi < ngroups; gi += stride) {
+    const int64_t g0 = gi * GSTATS_ROWS;
+    const int last = (int)(n - g0 < GSTATS_ROWS ? n - g0 : GSTATS_ROWS) - 1;
+    float m = 0.f, mn = 3.0e38f;
+#pragma unroll
+    for (int j = 0; j < GSTATS_ROWS / 64; ++j) {
+      const int i = lane + 64 * j;
+      const float v = xn[g0 + (i < last ? i : last)];
+      m = fmaxf(m, v);
+      mn = fminf(mn, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      m = fmaxf(m, __shfl_xor(m, o, 64));
+      mn = fminf(mn, __shfl_xor(mn, o, 64));
+    }
+    if (lane == 0) { out[2 * gi] = m; out[2 * gi + 1] = mn; }
+  }
+}
+
+hipError_t launch_group_norm_stats(const float* xn, int64_t n, int64_t row0, float* out, hipStream_t s) {
+  if (row0 < 0 || row0 % GSTATS_ROWS != 0) return hipErrorInvalidValue;
+  if (n <= 0) return hipSuccess;
+  const int64_t ngroups = (n + GSTATS_ROWS - 1) / GSTATS_ROWS;
+  int64_t nb = (ngroups + 3) / 4;
+  if (nb > 16384) nb = 16384;
+  hipLaunchKernelGGL(group_norm_stats_kernel, dim3((unsigned)nb), dim3(256), 0, s, xn, n, ngroups, out);
+  return hipGetLastError();
+}
+
 // Packed 16-bit helpers, written out (left to itself the compiler turns min(y, 1) per half into
 // a compare + select per half, six instructions for one).
 __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {

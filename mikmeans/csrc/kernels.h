@@ -91,7 +91,17 @@ struct AssignArgs {
   // launcher-set (A/B switch V_ASSIGN_EARLY): norms first, fragments in flight across the
   // seed-offset barrier (plain full bf16 rows with caller norms)
   int early_prologue = 1;
+  // optional per-group seed statistics of a plain full pass (launch_group_norm_stats over this call's xn,
+  // f32 pairs): group g's (max, min) |x|^2 -- the bf16 kernels whose workgroup is GSTATS_ROWS rows read their
+  // seed decision from it instead of reducing the norms (early prologue, persistent kernel); the values,
+  // and so every key, are the same.  nullptr, or any other path: the kernel's own reduction.
+  const float* gstats = nullptr;
 };
+// (max, min) of xn over each GSTATS_ROWS-row group of the one-pass grid, the last over its valid rows: the
+// folds of the assign's seed rule (fmaxf from 0, fminf from 3e38).  X and so xn are fixed for a fit: once
+// per fit.  row0: the global row of xn[0], which must lie on the group grid (ROW_ALIGN shards do).
+constexpr int GSTATS_ROWS = 256;
+hipError_t launch_group_norm_stats(const float* xn, int64_t n, int64_t row0, float* out, hipStream_t s);
 // Profiling hook: every assign16 launch writes its workgroups' timelines to buf (nullptr: off;
 // the caller sizes it for the grid, 8 u64 per workgroup, capacity in workgroups)
 void set_assign_timeline(unsigned long long* buf, int64_t capacity);

@@ -61,6 +61,13 @@ class IterStats:
         }
 
 
+# A resident fit builds the assign's per-group seed statistics by default: with them the headline assign
+# (bf16 D=128 K=1024, N=1e8) ran 18.12 -> 17.79 ms in the one-process A/B against the kernels before,
+# 3.4 times the noisier arm's spread, the same bits (profiles/r15_01_group_stats.md).  One pass over xn
+# and 8 bytes per 256 rows (parallel/memplan.py group_stats_bytes plans them).
+GROUP_STATS = True
+
+
 class LloydEngine:
     """Device-resident Lloyd state for one rank's shard of points.
 
@@ -69,12 +76,19 @@ class LloydEngine:
     engine is driven by :meth:`step` / :meth:`run`.
     """
 
+    gstats = None   # the full assign's per-group seed statistics (``group_stats``), resident fits only
+
     def __init__(self, X: torch.Tensor, n_clusters: int, *, comm: Comm | None = None,
                  sample_weight: torch.Tensor | None = None, frozen=None,
                  empty_policy: str = "keep", n_features: int | None = None, segments: int = 1,
                  overlap_sw: int = 8, incremental: bool = False, delta_cap: float = 0.125,
-                 spherical: bool = False, bounded: bool = False, tighten: bool = False):
+                 spherical: bool = False, bounded: bool = False, tighten: bool = False,
+                 group_stats: bool = GROUP_STATS):
         from ..ops import pad_columns
+
+        # The full assign's per-group seed statistics (max / min |x|^2 of each 256-row group), once per
+        # fit instead of in every workgroup of every step (ops.CentroidPack.group_stats); same bits.
+        self.group_stats = bool(group_stats)
 
         # Bounded E-step (Hamerly 2010): per-point bounds on the distance to the assigned
         # centre (ub) and to the second nearest (lb), moved by each M-step's centre shifts;
@@ -185,6 +199,7 @@ class LloydEngine:
         if self.n and not fused:
             C.row_sqnorm(self.X, self.xn)
         self.stats = col_stats(self.X, xn=self.xn if fused else None)   # (also the tol scale's sums: api.fit)
+        self.gstats = self.pk.group_stats(self.xn) if self.group_stats and self.n else None
         self.scales = mstep_scales(self.X, self.weights, comm=self.comm, stats=self.stats)
         if self.scales.nw and C.update_slice_width(self.dt, self.K, self.Dp, self.weights is not None) == 0:
             self.scales = MStepScales(self.scales.col_exp, self.scales.cnt_exp, [], dev)
@@ -259,6 +274,8 @@ class LloydEngine:
             t["wdot_scratch"] = self._wscratch
         if self.mind is not None:
             t["mind"] = self.mind
+        if getattr(self, "gstats", None) is not None:
+            t["gstats"] = self.gstats
         if self.pk._keys is not None:
             t["split_keys"] = self.pk._keys
         if self.delta is not None:
@@ -487,7 +504,7 @@ class LloydEngine:
                 if self.bounded:
                     self._bounded_assign()
                 else:
-                    self.pk.assign(self.X, self.xn, self.labels, self.mind, self.slots, True)
+                    self.pk.assign(self.X, self.xn, self.labels, self.mind, self.slots, True, gstats=self.gstats)
             with _phase("mikmeans.update"):
                 d = self.delta
                 if d is not None:
@@ -569,7 +586,9 @@ class LloydEngine:
         kd, nc = self.K * self.Dp, self.seg_chunks
         for s, (r0, r1) in enumerate(self.seg_ranges):
             mind = self.mind[r0:r1] if self.mind is not None else None
-            self.pk.assign(self.X[r0:r1], self.xn[r0:r1], self.labels[r0:r1], mind, self.slots, True)
+            # (segments start on the 1536-row grid: whole groups of the table)
+            gs = self.gstats[r0 // 256: -(-r1 // 256)] if self.gstats is not None else None
+            self.pk.assign(self.X[r0:r1], self.xn[r0:r1], self.labels[r0:r1], mind, self.slots, True, gstats=gs)
             self.seg_events[s].record(main)
         C.set_update_max_sw(self.overlap_sw)
         try:
@@ -655,7 +674,7 @@ class LloydEngine:
 
     def _assign_into(self, mind):
         labels = torch.empty_like(self.labels)
-        self.pk.assign(self.X, self.xn, labels, mind)
+        self.pk.assign(self.X, self.xn, labels, mind, gstats=self.gstats)
 
     def last_stats(self) -> IterStats:
         """Host read of the last iteration's scalars (one small D2H copy)."""
@@ -695,7 +714,7 @@ class LloydEngine:
             mind = torch.empty(self.n, dtype=torch.float32, device=self.device) if with_dist else None
             if self.n:
                 xn = self.xn if with_dist else None
-                self.pk.assign(self.X, xn, labels, mind)
+                self.pk.assign(self.X, xn, labels, mind, gstats=self.gstats if with_dist else None)
             return labels, mind
         return cpu_ops.assign(self.X, self.C, with_dist=with_dist, xn=self.xn)
 

@@ -98,14 +98,16 @@ class CentroidPack:
                          self.dpad, self.Kpad, qshift)
 
     def assign(self, X, xn, labels, mind=None, slots=None, track_changed: bool = False, rows=None,
-               ub=None, lb=None, scatter: bool = False, count=None, oseed=None):
+               ub=None, lb=None, scatter: bool = False, count=None, oseed=None, gstats=None):
         """K2 on these centres (``X`` column-padded, 16-B rows).  ``rows`` (int64, device):
         assign the gathered batch X[rows] without materialising it (labels etc. logical, or
         at the rows themselves with ``scatter``).  ``ub`` / ``lb``: also write every point's
         distance to its nearest and second-nearest centre (the bounded E-step's bounds).
         ``count`` (int64 [1], device): assign only ``rows[:count]`` (a compacted batch).
         ``oseed`` (bf16, f32 [X rows]): every row's seed offset, from :func:`seed_offsets` --
-        a gathered row then gets bitwise the scores (and label) of the full pass over ``X``."""
+        a gathered row then gets bitwise the scores (and label) of the full pass over ``X``.
+        ``gstats`` (bf16, from :meth:`group_stats` of this ``xn``): the row groups' seed statistics,
+        computed once where ``X`` stays for many calls; the outputs are the same bits without it."""
         if rows is not None:
             self._C.assign(X, self.pack, self.cn, xn, labels, mind, slots, self.Kpad, self.dpad,
                            track_changed, None, rows, ub, lb, scatter, count, oseed)
@@ -119,8 +121,23 @@ class CentroidPack:
             keys = self._keys
             if xn is not None and mind is None:   # the splits park each point's seed offset there
                 mind = torch.empty(X.shape[0], dtype=torch.float32, device=X.device)
+        if keys is not None or xn is None:   # (the table is the plain one-launch pass's)
+            gstats = None
         self._C.assign(X, self.pack, self.cn, xn, labels, mind, slots, self.Kpad, self.dpad,
-                       track_changed, keys, None, ub, lb, False, None, oseed)
+                       track_changed, keys, None, ub, lb, False, None, oseed, gstats)
+
+    def group_stats(self, xn: torch.Tensor, row0: int = 0) -> "torch.Tensor | None":
+        """(max, min) of ``xn`` over each row group of the full assign, f32 [groups, 2]
+        (csrc/finalize.hip group_norm_stats): what every bf16 workgroup otherwise reduces again in
+        every call.  None where no kernel reads it: anything but bf16 rows of 65..128 features in
+        256-row groups (parallel/memplan.py ``group_stats_bytes`` plans the same rule)."""
+        C = self._C
+        if (self.dtype != torch.bfloat16 or self.dpad != 128
+                or C.assign_block_rows(self.dt, self.dpad, self.Kpad) != C.GSTATS_ROWS):
+            return None
+        out = torch.empty((-(-xn.numel() // C.GSTATS_ROWS), 2), dtype=torch.float32, device=xn.device)
+        C.group_norm_stats(xn, out, row0)
+        return out
 
     def seed_offsets(self, xn: torch.Tensor) -> "torch.Tensor | None":
         """Per-row seed offsets the full assign over rows with norms ``xn`` gives its bf16

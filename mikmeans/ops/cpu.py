@@ -31,6 +31,19 @@ def scores(X: torch.Tensor, centers: torch.Tensor) -> torch.Tensor:
     return (c * c).sum(1)[None, :] - 2.0 * (Xf @ c.T)
 
 
+def group_norm_stats(xn: torch.Tensor, rows: int = 256) -> torch.Tensor:
+    """(max, min) of ``xn`` over each ``rows``-row group, f32 [groups, 2]; the last group over its
+    valid rows.  The folds start from 0 and 3e38 as the assign kernels' do (norms are >= 0)."""
+    n = xn.numel()
+    out = torch.empty((-(-n // rows), 2), dtype=torch.float32)
+    v = xn.detach().to("cpu", torch.float32).reshape(-1)
+    for gi in range(out.shape[0]):
+        blk = v[gi * rows: min(n, (gi + 1) * rows)]
+        out[gi, 0] = torch.clamp(blk.max(), min=0.0)
+        out[gi, 1] = torch.clamp(blk.min(), max=3.0e38)
+    return out
+
+
 def assign(X: torch.Tensor, centers: torch.Tensor, *, with_dist: bool = True, xn=None):
     n = X.shape[0]
     labels = torch.empty(n, dtype=torch.int32, device=X.device)

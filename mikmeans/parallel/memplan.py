@@ -296,6 +296,17 @@ def _setup_items(n: int, Dp: int, es: int) -> dict:
     return {"colstat_part": _r(colstat_rows(es, n, Dp) * 3 * Dp * 8)} if n else {}
 
 
+GSTATS_ROWS = 256   # csrc/kernels.h: rows per group of the assign's per-group seed statistics
+
+
+def group_stats_bytes(n: int, Dp: int, es: int) -> int:
+    """Bytes of the full assign's per-group seed statistics (ops.CentroidPack.group_stats): an f32
+    pair per 256-row group, for bf16 rows of 65..128 padded features; 0 where no kernel reads them."""
+    if es != 2 or dpad_for(Dp, es) != 128 or n <= 0:
+        return 0
+    return _cdiv(n, GSTATS_ROWS) * 8
+
+
 def plan_resident(n: int, D: int, K: int, dtype="bfloat16", *, weighted: bool = False,
                   incremental: bool = True, init="k-means++", n_local_trials: int | None = None,
                   copy_x: bool = True, empty_policy: str = "keep", bounded: bool = False,
@@ -314,6 +325,8 @@ def plan_resident(n: int, D: int, K: int, dtype="bfloat16", *, weighted: bool = 
         p["weights"] = _r(n * 4)
     p["labels"] = _r(n * 4)
     p["xn"] = _r(n * 4)
+    if group_stats_bytes(n, Dp, es):
+        p["gstats"] = _r(group_stats_bytes(n, Dp, es))   # the assign's per-group seed statistics, once per fit
     if weighted or empty_policy == "farthest":
         p["mind"] = _r(n * 4)          # written by every step's assign (relocation reads it)
     if weighted:

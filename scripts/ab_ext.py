@@ -479,6 +479,9 @@ def cmd_run(a) -> int:
     dpad = native.dpad_for(eng.Dp, dt)
     per = {}
     for tag, m in mods.items():
+        for kv in filter(None, (a.set or "").split(",")):   # the same A/B switches on every module
+            name, v = kv.split("=")
+            m.set_variant([x.lower() for x in m.variant_names()].index(name.strip().lower()), int(v))
         kpad = m.assign_kpad(code, dpad, a.k)
         pack = torch.zeros(kpad * dpad, dtype=dt, device=dev)
         cn = torch.zeros(m.assign_cn_len(kpad), dtype=torch.float32, device=dev)
@@ -487,10 +490,19 @@ def cmd_run(a) -> int:
         mind = torch.empty(a.n, dtype=torch.float32, device=dev)
         slots = torch.zeros(m.NSLOT * m.SLOT_STRIDE, dtype=torch.float64, device=dev)
         per[tag] = dict(m=m, pack=pack, cn=cn, kpad=kpad, lab=lab, mind=mind, slots=slots, ts=[])
+        # a module with the per-group seed statistics (group_norm_stats) runs as two arms: with its table
+        # (built once, as a fit does) and, "<tag> no table", reducing the norms in every workgroup
+        if a.what == "assign" and hasattr(m, "group_norm_stats") and dt == torch.bfloat16 \
+                and m.assign_block_rows(code, dpad, kpad) == m.GSTATS_ROWS:
+            gs = torch.empty((-(-a.n // m.GSTATS_ROWS), 2), dtype=torch.float32, device=dev)
+            m.group_norm_stats(eng.xn, gs, 0)
+            per[tag + " no table"] = dict(per[tag], lab=torch.empty_like(lab), mind=torch.empty_like(mind),
+                                          slots=torch.zeros_like(slots), ts=[])
+            per[tag]["kw"] = {"gstats": gs}
 
     def run_assign(t):
         t["m"].assign(eng.X, t["pack"], t["cn"], eng.xn, t["lab"], t["mind"], t["slots"], t["kpad"], dpad, True,
-                      None)
+                      None, **t.get("kw", {}))
 
     if a.what == "update":   # one set of inputs per --mode (the head's), the same for every module
         from mikmeans import ops
@@ -655,6 +667,7 @@ def main(argv=None) -> int:
     r.add_argument("--d", type=int, default=None, help="features (default 128)")
     r.add_argument("--k", type=int, default=None, help="centres (default 1024)")
     r.add_argument("--dtype", default="bf16")
+    r.add_argument("--set", default=None, help="kernel switches set on every module, e.g. assign_persist=1")
     r.add_argument("--rounds", type=int, default=5)
     r.add_argument("--reps", type=int, default=5)
     r.add_argument("--what", default="assign", choices=["assign", "update", "blobs", "colstats", "rownorms",

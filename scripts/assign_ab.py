@@ -46,6 +46,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--arms", default="assign_early=0;assign_early=1")
+    ap.add_argument("--table", type=int, default=0,
+                    help="1: the full assign reads the per-group seed statistics (LloydEngine group_stats)")
     ap.add_argument("--gather", type=int, default=0,
                     help="> 0: time the gathered assign of this many random rows (the mini-batch "
                          "resident path: X[rows] read in place, norms from the fragments)")
@@ -54,7 +56,7 @@ def main():
     dev = torch.device("cuda")
     comm = Comm.local(dev)
     X = make_blobs(a.n, a.d, a.k, seed=0, dtype=dt, device=dev, centers=blob_centers(a.k, a.d, 10.0, 0, device=dev))
-    eng = LloydEngine(X, a.k, comm=comm).set_centers(init_random(X, a.d, a.k, a.n, 0, comm, 0))
+    eng = LloydEngine(X, a.k, comm=comm, group_stats=bool(a.table)).set_centers(init_random(X, a.d, a.k, a.n, 0, comm, 0))
     for _ in range(3 if not a.gather else 1):
         eng.step()
     if a.gather:
@@ -66,7 +68,7 @@ def main():
             eng.pk.assign(eng.X, None, glab, None, eng.slots, False, rows=rows)
     else:
         def call():
-            eng.pk.assign(eng.X, eng.xn, eng.labels, eng.mind, eng.slots, True)
+            eng.pk.assign(eng.X, eng.xn, eng.labels, eng.mind, eng.slots, True, gstats=eng.gstats)
     arms = [parse_arm(s) for s in a.arms.split(";")]
     names = [s or "default" for s in a.arms.split(";")]
     labels = {}
@@ -106,7 +108,7 @@ def main():
             labels.setdefault(n, lab)
     ref = labels[names[0]]
     res = {"n": a.n, "d": a.d, "k": a.k, "dtype": a.dtype, "rounds": a.rounds, "reps": a.reps,
-           "gathered_rows": a.gather}
+           "gathered_rows": a.gather, "table": a.table}
     m = a.gather or a.n
     kpad = eng.pk.Kpad
     # MFMA instructions per SIMD: 16-point blocks x 16-centre tiles x K-steps of 32 (bf16) / 4 x 4 (f32)

@@ -29,12 +29,13 @@ def main():
     ap.add_argument("--d", type=int, default=128)
     ap.add_argument("--k", type=int, default=1024)
     ap.add_argument("--arm", default="", help="kernel switches, e.g. assign_early=0")
+    ap.add_argument("--table", type=int, default=0, help="1: the launch reads the per-group seed statistics")
     a = ap.parse_args()
     dev = torch.device("cuda")
     comm = Comm.local(dev)
     X = make_blobs(a.n, a.d, a.k, seed=0, dtype=torch.bfloat16, device=dev,
                    centers=blob_centers(a.k, a.d, 10.0, 0, device=dev))
-    eng = LloydEngine(X, a.k, comm=comm).set_centers(init_random(X, a.d, a.k, a.n, 0, comm, 0))
+    eng = LloydEngine(X, a.k, comm=comm, group_stats=bool(a.table)).set_centers(init_random(X, a.d, a.k, a.n, 0, comm, 0))
     for _ in range(2):
         eng.step()
     for kv in filter(None, a.arm.split(",")):
@@ -43,9 +44,9 @@ def main():
     C = native.require()
     cap = a.n // 16 + 1
     buf = torch.zeros(cap * 8, dtype=torch.int64, device=dev)
-    eng.pk.assign(eng.X, eng.xn, eng.labels, eng.mind, eng.slots, True)   # warm
+    eng.pk.assign(eng.X, eng.xn, eng.labels, eng.mind, eng.slots, True, gstats=eng.gstats)   # warm
     C.set_assign_timeline(buf)
-    eng.pk.assign(eng.X, eng.xn, eng.labels, eng.mind, eng.slots, True)
+    eng.pk.assign(eng.X, eng.xn, eng.labels, eng.mind, eng.slots, True, gstats=eng.gstats)
     torch.cuda.synchronize()
     C.set_assign_timeline(None)
     t = buf.view(-1, 8).cpu().numpy()
@@ -64,7 +65,7 @@ def main():
     out_land = {"median": float(np.median(land)), "p90": float(np.percentile(land, 90))}
     frag = (t[:, 7] - t0 - ent) * us
     out_frag = {"median": float(np.median(frag)), "p90": float(np.percentile(frag, 90))}
-    out = {"n": a.n, "d": a.d, "k": a.k, "arm": a.arm, "workgroups": int(len(t)),
+    out = {"n": a.n, "d": a.d, "k": a.k, "arm": a.arm, "table": a.table, "workgroups": int(len(t)),
            "kernel_us": float((ext.max()) * us),
            "prologue_us": {"median": float(np.median(pro)), "p90": float(np.percentile(pro, 90))},
            "loads_landed_us": out_land,
