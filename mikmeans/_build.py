@@ -25,7 +25,8 @@ CSRC = PKG / "csrc"
 BUILD = PKG.parent / "build" / "native"
 ARCH = os.environ.get("MIKMEANS_ARCH", "gfx950")
 HIP_SOURCES = ["assign16.hip", "update.hip", "finalize.hip", "kpp.hip", "rows.hip", "transform.hip", "topk.hip",
-               "quality.hip", "exemplars.hip", "quantiles.hip", "ivf.hip", "range.hip", "deep.hip", "pq.hip"]
+               "quality.hip", "exemplars.hip", "quantiles.hip", "ivf.hip", "range.hip", "deep.hip", "pq.hip",
+               "rerank.hip"]
 BINDING = "binding.cpp"
 
 DEVICE_FLAGS = [
@@ -44,7 +45,9 @@ DEVICE_FLAGS = [
 # Per-source extras.  The assign kernel: no SLP vectorizer, so the MFMA seed adds stay
 # scalar v_add_f32 (packed v_pk_add_f32 seeds intermittently corrupted a point block's
 # scores on gfx950; see seed_add in common.h).
-SOURCE_FLAGS = {"assign16.hip": ["-fno-slp-vectorize"]}
+# The re-rank kernel: no fma contraction, its
+# subtract, multiply and add are rounded one by one (docs/PQ_INDEX.md defines the distance so).
+SOURCE_FLAGS = {"assign16.hip": ["-fno-slp-vectorize"], "rerank.hip": ["-ffp-contract=off"]}
 
 
 def source_flags(name: str, csrc: Path = CSRC) -> list[str]:

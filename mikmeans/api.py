@@ -671,7 +671,47 @@ class PQIndex:
         a, b = (int(v) for v in self._index.offsets[int(k) : int(k) + 2])
         return self._index.order[a:b] + self.row_start
 
-    def search(self, Q, m: int, *, nprobe: int = 8, squared: bool = False):
+    def _search_refined(self, Q, m: int, nprobe: int, squared: bool, refine, shortlist):
+        """:meth:`search` with ``refine``: the shortlists of ``ops.pq_shortlist`` re-ranked on the rows."""
+        mdl, ix = self._model, self._index
+        if getattr(mdl, "metric", "euclidean") == "cosine":
+            raise NotImplementedError("PQIndex.search(refine=) is not available for cosine models")
+        ops.pq_shortlist_groups(32 if shortlist is None else shortlist)
+        shortlist = 32 if shortlist is None else int(shortlist)
+        c = mdl.cluster_centers_
+        K, F, dev = int(c.shape[0]), int(c.shape[1]), ix.codes.device
+        if torch.is_tensor(refine):
+            X = refine
+        else:
+            import warnings
+
+            with warnings.catch_warnings():     # (a read-only memory map: the rows are only ever read)
+                warnings.simplefilter("ignore", UserWarning)
+                X = torch.from_numpy(np.asarray(refine))
+        if X.dim() != 2 or tuple(X.shape) != (ix.n, F):
+            raise ValueError(f"refine takes the rows the index was built over, [{ix.n}, {F}], got shape {tuple(X.shape)}")
+        if X.is_cuda and (X.dtype != ix.dtype or X.device != dev):
+            raise ValueError(f"refine takes device rows of {ix.dtype} on {dev} (they are read in place), got "
+                             f"{X.dtype} on {X.device}; pass them from the host or convert them")
+        host = not X.is_cuda and ix.codes.is_cuda
+        if not X.is_cuda and not host and X.dtype != ix.dtype:
+            X = X.to(ix.dtype)
+        if ix.codes.is_cuda:
+            from .parallel import memplan
+
+            plan = memplan.plan_pq_refine(ix.n, F, K, ix.M, ix.dtype, nq=int(Q.shape[0]), m=m, nprobe=nprobe,
+                                          shortlist=shortlist, host_rows=host)
+            plan.budget = memplan.hbm_budget(dev) + sum(
+                plan.persistent[k] for k in ("codes", "order", "offsets", "codebooks"))   # (held already)
+            if not plan.fits:
+                raise memplan.HBMCapacityError(f"search: {plan.summary()} does not fit")
+        (keys,), was_numpy = mdl._row_blocks(
+            Q, lambda Qt, pk: (ops.pq_refine(ix, Qt, c, X, m, nprobe, shortlist, pack=pk),))
+        rows, d2 = ops.index_decode(keys, row_start=self.row_start)
+        d = d2 if squared else d2.sqrt()
+        return (rows.cpu().numpy(), d.cpu().numpy()) if was_numpy else (rows, d)
+
+    def search(self, Q, m: int, *, nprobe: int = 8, squared: bool = False, refine=None, shortlist=None):
         """The ``m`` indexed rows of least asymmetric distance to every query among the lists of its
         ``nprobe`` nearest centres: ``(rows [nq, m] int64, distances [nq, m] float32)``, nearest first
         and equal distances by the lower row id; padding is row -1 and distance NaN.  ``1 <= m <= 32``
@@ -680,7 +720,19 @@ class PQIndex:
         distance to the row itself.  On the GPU: the top-``nprobe`` kernel, the transform kernel for
         the tables and the scan of csrc/pq.hip, one workgroup per (query, probed list, split) with the
         table in LDS; the memory plan (``memplan.plan_pq_search``) is checked against the HBM budget up
-        front.  Results are bitwise the same from run to run.  numpy in, numpy out."""
+        front.  Results are bitwise the same from run to run.  numpy in, numpy out.
+
+        ``refine=X`` re-ranks on the rows themselves: ``X`` ``[n_rows, n_features]`` (numpy or torch, host
+        or device) holds the rows the index was built over, the codes pick ``shortlist`` rows of every
+        probed list (``ops.pq_shortlist``: 1..32, or 64, 96, ..., 256; default 32) and the result is the
+        ``m`` of them of least exact distance -- ``ops.rerank``'s float32 sum of squared differences
+        (``squared``), or its square root -- equal distances by the lower row id.  Device rows must be in
+        the model's dtype on the index's device and are read in place (csrc/rerank.hip).  Host rows
+        of a GPU index cost one host read per block of queries: the block's candidate ids go to the
+        host, the distinct rows are gathered there, cross to the device once in the model's dtype and
+        meet the same kernel, so the result is bit for bit the one with device rows.  The memory plan
+        is ``memplan.plan_pq_refine``.  Cosine models raise ``NotImplementedError``; ``shortlist``
+        without ``refine`` is a ``ValueError``."""
         mdl, ix = self._model, self._index
         m = int(m)
         if not 1 <= m <= ops.INDEX_MAX_M:
@@ -691,6 +743,10 @@ class PQIndex:
             raise ValueError(f"search needs 1 <= nprobe <= n_clusters ({K}), got nprobe = {nprobe}")
         if getattr(Q, "ndim", 2) != 2:
             raise ValueError(f"Q must be 2-D [n_queries, n_features], got shape {tuple(Q.shape)}")
+        if refine is None and shortlist is not None:
+            raise ValueError("search takes shortlist only with refine=X, the rows to re-rank on")
+        if refine is not None:
+            return self._search_refined(Q, m, nprobe, squared, refine, shortlist)
         if ix.codes.is_cuda:
             from .parallel import memplan
 

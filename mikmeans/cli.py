@@ -200,6 +200,8 @@ def cmd_search(a) -> int:
     if a.radius is not None:
         if a.deep:
             raise SystemExit("search: --deep goes with --top M")
+        if a.refine is not None or a.shortlist is not None:
+            raise SystemExit("search: --refine and --shortlist go with --top M on a PQ index")
         return _search_radius(a, km, comm)
     most = ops.INDEX_DEEP_MAX_M if a.deep else ops.INDEX_MAX_M
     if not 1 <= a.top <= most:
@@ -208,7 +210,21 @@ def cmd_search(a) -> int:
         raise SystemExit(f"search: --nprobe must be in [1, {K}], got {a.nprobe}")
     index, n = _search_index(a, km, comm)
     Q = np.load(a.queries, allow_pickle=False)
-    rows, dist = (index.search_deep if a.deep else index.search)(Q, a.top, nprobe=a.nprobe, squared=a.squared)
+    refined = {}
+    if a.refine is not None or a.shortlist is not None:
+        from . import PQIndex
+
+        if not isinstance(index, PQIndex) or a.refine is None:
+            raise SystemExit("search: --refine ROWS.npy [--shortlist S] re-ranks a PQ index (--index DIR of index --pq)")
+        # (memory-mapped: the rows stay on the host and only the shortlisted ones are read)
+        refined = {"refine": np.load(a.refine, mmap_mode="r", allow_pickle=False), "shortlist": a.shortlist}
+    try:
+        rows, dist = (index.search_deep if a.deep else index.search)(Q, a.top, nprobe=a.nprobe, squared=a.squared,
+                                                                     **refined)
+    except ValueError as e:
+        if not refined:
+            raise
+        raise SystemExit(f"search: {e}")
     if comm.rank == 0:
         if a.output:
             np.savez(a.output, rows=rows.astype(np.int64), distances=dist.astype(np.float32))
@@ -595,6 +611,11 @@ def build_parser():
                          "radius); writes lims, rows and distances")
     sp.add_argument("--nprobe", type=int, default=8, metavar="P",
                     help="clusters searched per query (1..n_clusters; n_clusters = exact search)")
+    sp.add_argument("--refine", metavar="ROWS.npy",
+                    help="with a PQ index: re-rank every probed list's shortlist on these rows (the ones the index was "
+                         "built over; memory-mapped), PQIndex.search(refine=)")
+    sp.add_argument("--shortlist", type=int, metavar="S",
+                    help="with --refine: rows the codes keep of every probed list (1..32, or 64, 96, ..., 256; default 32)")
     sp.add_argument("--squared", action="store_true", help="write squared distances")
     sp.add_argument("--output", help="write rows and distances here (.npz)")
     sp.add_argument("--device")

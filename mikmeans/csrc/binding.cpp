@@ -493,6 +493,37 @@ void pq_scan(const Tensor& codes, const Tensor& order, const Tensor& offsets, co
   hip_check(mk::launch_pq_scan(a, stream()), "pq_scan");
 }
 
+// The re-rank of candidates against the rows (csrc/rerank.hip): out [nq, R] keys
+void rerank(const Tensor& Q, const Tensor& X, const Tensor& cand, const Tensor& out) {
+  check_cuda(Q, "Q");
+  check_cuda(X, "X");
+  const int dt = dtype_of(X);
+  TORCH_CHECK(Q.scalar_type() == X.scalar_type(), "mikmeans: rerank takes queries and rows of one dtype");
+  TORCH_CHECK(Q.dim() == 2 && X.dim() == 2 && Q.size(1) == X.size(1) && Q.size(1) >= 1,
+              "mikmeans: rerank takes Q [nq, F] and X [n, F]");
+  const int64_t nq = Q.size(0), n = X.size(0), F = Q.size(1);
+  TORCH_CHECK(F <= INT32_MAX && n < (int64_t(1) << 32), "mikmeans: rerank takes fewer than 2^32 rows");
+  // (a tensor of one row or one column may carry any stride: the kernel is told F)
+  const int64_t ldq = nq <= 1 ? F : Q.stride(0), ldx = n <= 1 ? F : X.stride(0);
+  TORCH_CHECK((F == 1 || (Q.stride(1) == 1 && X.stride(1) == 1)) && ldq >= F && ldx >= F,
+              "mikmeans: rerank takes rows with unit column stride and a row stride >= F");
+  TORCH_CHECK(cand.dim() == 2 && cand.size(0) == nq && cand.size(1) >= 1, "mikmeans: cand must be [nq, R], R >= 1");
+  const int64_t R = cand.size(1);
+  check_i64(cand, "cand", nq * R);
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == nq && out.size(1) == R, "mikmeans: out must be [nq, R]");
+  check_i64(out, "out", nq * R);
+  const int dev = Q.get_device();
+  for (const Tensor* t : {&X, &cand, &out})
+    TORCH_CHECK(t->get_device() == dev, "mikmeans: rerank tensors must share a device");
+  mk::RerankArgs a;
+  a.Q = Q.data_ptr(); a.ldq = ldq; a.X = X.data_ptr(); a.ldx = ldx; a.n = n; a.F = (int)F;
+  a.cand = cand.data_ptr<int64_t>(); a.nq = nq; a.R = R;
+  a.run = mk::rr_run(nq, R); a.runs = mk::rr_runs(R, a.run); a.items = mk::rr_items(nq, R, a.run);
+  TORCH_CHECK(nq == 0 || (a.items > 0 && mk::rr_grid(a.items) > 0), "mikmeans: too many candidates for one rerank launch");
+  a.out = reinterpret_cast<long long*>(out.data_ptr<int64_t>());
+  hip_check(mk::launch_rerank(dt, a, stream()), "rerank");
+}
+
 void quality_accumulate(const Tensor& idx, const Tensor& d2, const Tensor& table, int64_t path) {
   TORCH_CHECK(table.dim() == 2 && table.size(1) == mk::QUALITY_WORDS, "mikmeans: table must be [K, ",
               mk::QUALITY_WORDS, "]");
@@ -1275,6 +1306,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "workgroups that share one (query, probed list) pair of a pq_scan over npairs pairs");
   m.def("pq_lds_bytes", [](int64_t M, int64_t m_) { return mk::pq_lds_bytes((int)M, (int)m_); });
   m.attr("PQ_MAX_SPLITS") = mk::PQ_MAX_SPLITS;
+  m.def("rerank", &rerank,
+        "the exact squared distance of every (query, candidate row) as (d2 bits << 32 | row) keys, out [nq, R]; "
+        "IVF_EMPTY_KEY for an id outside [0, n)",
+        py::arg("Q"), py::arg("X"), py::arg("cand"), py::arg("out"));
+  m.def("rerank_run", [](int64_t nq, int64_t R) { return mk::rr_run(nq, R); },
+        "candidates a wave of a rerank over [nq, R] takes");
   m.def("quality_accumulate", &quality_accumulate,
         "add the top-2 output's per-cluster quality words into table [K, QUALITY_WORDS] (integer atomics)",
         py::arg("idx"), py::arg("d2"), py::arg("table"), py::arg("path") = -1);

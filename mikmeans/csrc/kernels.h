@@ -10,6 +10,7 @@
 #include "dispatch.h"   // for_width: the (dtype, padded width) switch of every launcher that has one
 #include "fold.h"       // the frame constants of the per-cluster folds (FOLD_*)
 #include "pqplan.h"     // the launch planning of the product-quantised scan (PQ_*, pq_scan_splits)
+#include "rerankplan.h" // the launch planning of the re-rank kernel (RR_*, rr_run)
 #include "walk.h"       // the work item of a walk over an index's lists, its grid bound, walk_blocks
 
 namespace mk {
@@ -291,6 +292,24 @@ struct PqScanArgs {
 };
 static_assert(PQ_MAX_M == TOPK_MAX && PQ_NW == 4, "csrc/pqplan.h mirrors the register-list kernels' constants");
 hipError_t launch_pq_scan(const PqScanArgs& a, hipStream_t s);
+
+// ---- the re-rank of candidates against the rows (csrc/rerank.hip) ----------------------------
+// out[q][j] = clamp_d2(|Q[q] - X[cand[q][j]]|^2) bits << 32 | cand[q][j] for every candidate id in
+// [0, n), IVF_EMPTY_KEY for any other id; an id that appears twice gives its key twice.  The sum is
+// the sixteen-accumulator order of docs/PQ_INDEX.md, subtract, multiply and add rounded one by
+// one.  Q and X are rows of one dtype with unit column stride and row strides ldq, ldx >= F
+// (in elements); pointers or strides off 16 bytes take element loads.  run / runs / items are
+// rr_run / rr_runs / rr_items of (nq, R) (csrc/rerankplan.h).  Bitwise the same on every launch.
+struct RerankArgs {
+  const void* Q; int64_t ldq;        // [nq, F]
+  const void* X; int64_t ldx;        // [n, F]
+  int64_t n; int F;
+  const int64_t* cand;               // [nq, R]
+  int64_t nq; int64_t R;
+  int run; int64_t runs; int64_t items;
+  long long* out;                    // [nq, R]
+};
+hipError_t launch_rerank(int dtype, const RerankArgs& a, hipStream_t s);
 
 // ---- per-cluster quality table (csrc/quality.hip) ----------------------------------------
 // Folds launch_topk's output (m = 1 or 2) into table[K][QUALITY_WORDS] (u64, only ever added

@@ -552,3 +552,81 @@ def pq_scan(index, lut: torch.Tensor, probes: torch.Tensor, m: int) -> torch.Ten
         key = torch.where(of >= 0, key, IVF_EMPTY_KEY).sort(dim=1).values[:, :m]
         keys[s : s + rows, : key.shape[1]] = key
     return keys
+
+
+def pq_shortlist(index, lut: torch.Tensor, probes: torch.Tensor, G: int, s: int) -> torch.Tensor:
+    """Shortlist keys int64 ``[nq, nprobe, G, s]`` (``ADC bits << 32 | row``, ``IVF_EMPTY_KEY`` padded):
+    position ``p`` of a probed list is in group ``(p // 256) mod G`` -- the chunks csrc/pqplan.h deals
+    to split ``g`` of ``G`` -- and every group keeps its ``s`` smallest keys, ascending."""
+    nq, nprobe = probes.shape
+    dev = lut.device
+    out = torch.full((nq, nprobe, G, s), IVF_EMPTY_KEY, dtype=torch.int64, device=dev)
+    offs = index.offsets.tolist()
+    pr = probes.tolist()
+    for q in range(nq):
+        for j in range(nprobe):
+            a, b = offs[pr[q][j]], offs[pr[q][j] + 1]
+            if a == b:
+                continue
+            pair = torch.full((1, b - a), q * nprobe + j, dtype=torch.int64, device=dev)
+            d = pq_adc(lut, pair, index.codes[a:b])[0]
+            key = (d.contiguous().view(torch.int32).to(torch.int64) << 32) | index.order[a:b]
+            group = (torch.arange(b - a, device=dev) // 256) % G
+            for g in range(min(G, (b - a + 255) // 256)):
+                k = key[group == g].sort().values[:s]
+                out[q, j, g, : k.numel()] = k
+    return out
+
+
+# ---- the re-rank of candidates against the rows (csrc/rerank.hip, csrc/rerankplan.h) ----------------
+RERANK_GROUP = 16                   # csrc/rerankplan.h RR_GROUP: the accumulators of a pair
+
+
+def rerank_keys(Q: torch.Tensor, X: torch.Tensor, cand: torch.Tensor) -> torch.Tensor:
+    """Keys int64 ``[nq, R]``, ``d2 bits << 32 | cand`` and ``IVF_EMPTY_KEY`` for an id outside ``[0, n)``,
+    in the order of adds of csrc/rerank.hip: pieces of ``V`` = 8 (bfloat16) or 4 columns, accumulator
+    ``s`` of sixteen takes the pieces ``s, s + 16, ...`` column after column as ``d = q - x``,
+    ``p = d * d``, ``a = a + p`` (``torch.sub`` / ``mul`` / ``add``: one rounding each), and the
+    accumulators meet as ``((a0+a1)+(a2+a3)) + ((a4+a5)+(a6+a7))`` plus the same over ``a8..a15``."""
+    nq, F = Q.shape
+    n, R = X.shape[0], cand.shape[1]
+    V = 8 if Q.dtype == torch.bfloat16 else 4
+    G = RERANK_GROUP
+    pieces = (F + V - 1) // V
+    rounds = (pieces + G - 1) // G
+    width = rounds * G * V
+    ok = (cand >= 0) & (cand < n)
+    keys = torch.empty((nq, R), dtype=torch.int64, device=Q.device)
+    rows = max(1, (1 << 24) // max(R * width, 1))
+    zero = torch.zeros((), dtype=torch.float32, device=Q.device)
+    for s in range(0, nq, rows):
+        okb = ok[s : s + rows]
+        c = torch.where(okb, cand[s : s + rows], 0)
+        nb = c.shape[0]
+        xf = (X[c.reshape(-1)].to(torch.float32).view(nb, R, F) if n else torch.zeros((nb, R, F), device=Q.device))
+        d = torch.sub(Q[s : s + rows].to(torch.float32)[:, None, :], xf)
+        p = torch.zeros((nb, R, width), dtype=torch.float32, device=Q.device)   # (a column >= F: 0 - 0, squared)
+        p[:, :, :F] = torch.mul(d, d)
+        p = p.view(nb, R, rounds, G, V)
+        a = torch.zeros((nb, R, G), dtype=torch.float32, device=Q.device)
+        for k in range(rounds):
+            for e in range(V):
+                a = torch.add(a, p[:, :, k, :, e])
+        h = [torch.add(torch.add(torch.add(a[..., o], a[..., o + 1]), torch.add(a[..., o + 2], a[..., o + 3])),
+                       torch.add(torch.add(a[..., o + 4], a[..., o + 5]), torch.add(a[..., o + 6], a[..., o + 7])))
+             for o in (0, 8)]
+        d2 = torch.add(h[0], h[1])
+        nan = torch.isnan(d2)               # (clamp_d2: one NaN pattern; a sum of squares is never negative)
+        bits = torch.where(nan, 0x7FC00000, torch.where(nan, zero, d2).contiguous().view(torch.int32).to(torch.int64))
+        keys[s : s + rows] = torch.where(okb, (bits << 32) | c, IVF_EMPTY_KEY)
+    return keys
+
+
+def rerank(Q: torch.Tensor, X: torch.Tensor, cand: torch.Tensor, m: int) -> torch.Tensor:
+    """The ``m`` smallest of :func:`rerank_keys` per query, ascending, ``IVF_EMPTY_KEY`` padded."""
+    keys = rerank_keys(Q, X, cand).sort(dim=1).values[:, :m]
+    if keys.shape[1] == m:
+        return keys
+    out = torch.full((Q.shape[0], m), IVF_EMPTY_KEY, dtype=torch.int64, device=Q.device)
+    out[:, : keys.shape[1]] = keys
+    return out

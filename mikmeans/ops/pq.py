@@ -15,6 +15,8 @@ table entries.  Everything is defined bit for bit (docs/PQ_INDEX.md):
 * :func:`pq_search`   the ``nprobe`` nearest centres of every query, the tables of its residuals and
   the scan of csrc/pq.hip: sorted ``(ADC bits << 32 | row)`` keys, decoded by
   :func:`mikmeans.ops.index_decode`
+* :func:`pq_shortlist` / :func:`rerank` / :func:`pq_refine`   the refined search: the scan picks a
+  shortlist of every probed list and csrc/rerank.hip ranks it by exact distances to the rows
 
 GPU tensors run the native kernels; CPU tensors run the mirrors of :mod:`mikmeans.ops.cpu` with the
 same tensors and the same order of adds.
@@ -28,7 +30,8 @@ from .index import INDEX_MAX_M, _nearest_lists, partition
 from .native import dpad_for, require
 
 __all__ = ["PQ_SUBVECTORS", "PQ_KSUB", "PQ_SCAN_BYTES", "PQ_ENCODE_ROWS", "PQRowIndex", "pq_check", "pq_train",
-           "pq_encode", "pq_lut", "pq_build", "pq_search", "pq_block_queries", "pq_reconstruct"]
+           "pq_encode", "pq_lut", "pq_build", "pq_search", "pq_block_queries", "pq_reconstruct", "pq_shortlist",
+           "pq_shortlist_groups", "pq_refine", "pq_refine_block_queries", "rerank"]
 
 PQ_SUBVECTORS = cpu.PQ_SUBVECTORS    # csrc/pqplan.h pq_subvectors_ok
 PQ_KSUB = cpu.PQ_KSUB                # codewords of a sub-space: a code is one byte
@@ -218,6 +221,30 @@ def pq_block_queries(M: int, m: int, nprobe: int, F: int, splits: int = 8) -> in
     return max(1, PQ_SCAN_BYTES // per)
 
 
+def _search_queries(index: PQRowIndex, Q: torch.Tensor, nprobe: int) -> torch.Tensor:
+    """The queries as the kernels take them (padded columns on the GPU), or the ValueError of a search."""
+    if not 1 <= nprobe <= index.K:
+        raise ValueError(f"search needs 1 <= nprobe <= n_clusters ({index.K}), got nprobe = {nprobe}")
+    if Q.dim() != 2:
+        raise ValueError(f"search needs queries [nq, D], got shape {tuple(Q.shape)}")
+    Qp = pad_columns(Q) if Q.is_cuda else Q
+    dev = index.codes.device
+    if Qp.shape[1] != index.D or Qp.dtype != index.dtype or Qp.device != dev:
+        raise ValueError(f"search needs queries of {index.D} {index.dtype} features on {dev}, got "
+                         f"{Qp.shape[1]} {Qp.dtype} on {Qp.device}")
+    return Qp
+
+
+def _block_tables(index: PQRowIndex, Qb: torch.Tensor, centers: torch.Tensor, cen: torch.Tensor, nprobe: int, pack):
+    """What a block of queries brings to the scan: ``(probes int32 [nb, nprobe], tables float32
+    [nb * nprobe, M, 256])`` -- :func:`mikmeans.ops.topk`'s nearest centres and the :func:`pq_lut` of
+    every query's residual against each of them.  ``cen``: the centres in float32."""
+    nb, F = Qb.shape[0], index.F
+    probes, _ = topk(Qb, centers, nprobe, pack=pack)
+    RQ = (Qb[:, None, :F].to(torch.float32) - cen[probes.to(torch.int64)]).to(index.dtype).view(nb * nprobe, F)
+    return probes, pq_lut(RQ, index.codebooks, packs=index.packs())
+
+
 def pq_search(index: PQRowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int, nprobe: int, *, pack=None,
               splits: int | None = None, block_queries: int | None = None) -> torch.Tensor:
     """The ``m`` indexed rows of least asymmetric distance to every query among the lists of its
@@ -232,15 +259,8 @@ def pq_search(index: PQRowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int,
     m, nprobe = int(m), int(nprobe)
     if not 1 <= m <= INDEX_MAX_M:
         raise ValueError(f"search needs 1 <= m <= {INDEX_MAX_M}, got m = {m}")
-    if not 1 <= nprobe <= index.K:
-        raise ValueError(f"search needs 1 <= nprobe <= n_clusters ({index.K}), got nprobe = {nprobe}")
-    if Q.dim() != 2:
-        raise ValueError(f"search needs queries [nq, D], got shape {tuple(Q.shape)}")
-    Qp = pad_columns(Q) if Q.is_cuda else Q
+    Qp = _search_queries(index, Q, nprobe)
     dev = index.codes.device
-    if Qp.shape[1] != index.D or Qp.dtype != index.dtype or Qp.device != dev:
-        raise ValueError(f"search needs queries of {index.D} {index.dtype} features on {dev}, got "
-                         f"{Qp.shape[1]} {Qp.dtype} on {Qp.device}")
     native = index.codes.is_cuda
     if splits is not None and not 1 <= int(splits) <= cpu.PQ_MAX_SPLITS:
         raise ValueError(f"search needs 1 <= splits <= {cpu.PQ_MAX_SPLITS}, got {splits}")
@@ -248,13 +268,10 @@ def pq_search(index: PQRowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int,
     cen = centers.to(torch.float32)
     keys = torch.empty((nq, m), dtype=torch.int64, device=dev)
     block = max(1, int(block_queries)) if block_queries else pq_block_queries(index.M, m, nprobe, F)
-    packs = index.packs()
     for s in range(0, nq, block):
         Qb = Qp[s : s + block]
         nb = Qb.shape[0]
-        probes, _ = topk(Qb, centers, nprobe, pack=pack)
-        RQ = (Qb[:, None, :F].to(torch.float32) - cen[probes.to(torch.int64)]).to(index.dtype).view(nb * nprobe, F)
-        lut = pq_lut(RQ, index.codebooks, packs=packs)
+        probes, lut = _block_tables(index, Qb, centers, cen, nprobe, pack)
         if not native:
             keys[s : s + block] = cpu.pq_scan(index, lut, probes, m)
             continue
@@ -263,6 +280,150 @@ def pq_search(index: PQRowIndex, Q: torch.Tensor, centers: torch.Tensor, m: int,
         out = torch.empty((nb * nprobe, sp, m), dtype=torch.int64, device=dev)
         C.pq_scan(index.codes, index.order, index.offsets, lut, probes.reshape(-1).contiguous(), sp, out)
         keys[s : s + block] = out.view(nb, nprobe * sp * m).sort(dim=1).values[:, :m]   # unique keys: one order
+    return keys
+
+
+def pq_shortlist_groups(shortlist: int) -> tuple[int, int]:
+    """``(G, s)`` of a shortlist of ``S`` rows a probed list: one group of ``S <= 32`` rows, or ``S // 32``
+    groups of 32 for ``S`` in 64, 96, ..., 256; a ValueError that names what is allowed otherwise."""
+    S = int(shortlist)
+    if 1 <= S <= INDEX_MAX_M:
+        return 1, S
+    if S % INDEX_MAX_M == 0 and 2 <= S // INDEX_MAX_M <= cpu.PQ_MAX_SPLITS:
+        return S // INDEX_MAX_M, INDEX_MAX_M
+    raise ValueError(f"a shortlist takes 1 <= shortlist <= {INDEX_MAX_M} rows a probed list or one of "
+                     f"{', '.join(str(INDEX_MAX_M * g) for g in range(2, cpu.PQ_MAX_SPLITS + 1))}, got {shortlist}")
+
+
+def pq_refine_block_queries(M: int, nprobe: int, F: int, shortlist: int, *, host_rows: bool = False,
+                            esize: int = 4) -> int:
+    """Queries per block of a refined search: :func:`pq_block_queries`'s terms at ``splits = G, m = s``,
+    a query's ``R = nprobe * shortlist`` candidate ids, its ``R`` re-rank keys with the sort's two copies
+    and, for rows kept on the host, the staged rows (at most ``R`` of ``F`` features of ``esize`` bytes)
+    and their remapped ids, within ``PQ_SCAN_BYTES``."""
+    R = int(nprobe) * int(shortlist)
+    per = int(nprobe) * (int(M) * PQ_KSUB * 4 + 8 * int(F) + 16 * int(shortlist)) + 32 * R
+    if host_rows:
+        per += R * (int(F) * int(esize) + 8)
+    return max(1, PQ_SCAN_BYTES // per)
+
+
+def _shortlist_blocks(index: PQRowIndex, Qp: torch.Tensor, centers: torch.Tensor, G: int, s: int, nprobe: int, pack,
+                      block: int):
+    """``(first query, candidate ids int64 [nb, nprobe * G * s])`` of every block of the checked queries ``Qp``."""
+    cen = centers.to(torch.float32)
+    dev = index.codes.device
+    for s0 in range(0, Qp.shape[0], block):
+        Qb = Qp[s0 : s0 + block]
+        nb = Qb.shape[0]
+        probes, lut = _block_tables(index, Qb, centers, cen, nprobe, pack)
+        if index.codes.is_cuda:
+            keys = torch.empty((nb * nprobe, G, s), dtype=torch.int64, device=dev)
+            require().pq_scan(index.codes, index.order, index.offsets, lut, probes.reshape(-1).contiguous(), G, keys)
+        else:
+            keys = cpu.pq_shortlist(index, lut, probes, G, s)
+        keys = keys.view(nb, nprobe * G * s)
+        yield s0, torch.where(keys == cpu.IVF_EMPTY_KEY, -1, keys & 0xFFFFFFFF)
+
+
+def pq_shortlist(index: PQRowIndex, Q: torch.Tensor, centers: torch.Tensor, shortlist: int, nprobe: int, *,
+                 pack=None, block_queries: int | None = None) -> torch.Tensor:
+    """The rows the codes pick for a re-rank: int64 ``[nq, nprobe * S]`` row ids, ``S = shortlist`` a
+    probed list, -1 for the empty slots.  ``1 <= S <= 32`` is one group of ``s = S`` rows; ``S`` in 64,
+    96, ..., 256 is ``G = S // 32`` groups of ``s = 32``.  Position ``p`` of a list (in ``order``) is in
+    group ``(p // 256) mod G``, and a group keeps its ``s`` rows of least ``(ADC bits, row id)``, the ADC
+    of :func:`pq_search`.  The slots run probe after probe (the nearest centre first), group after
+    group, ascending key within a group.  On the GPU: the scan of csrc/pq.hip with ``splits = G, m = s``,
+    whose split ``g`` takes exactly group ``g``.  The result does not depend on the blocking."""
+    G, s = pq_shortlist_groups(shortlist)
+    nprobe = int(nprobe)
+    Qp = _search_queries(index, Q, nprobe)
+    block = (max(1, int(block_queries)) if block_queries
+             else pq_refine_block_queries(index.M, nprobe, index.F, G * s))
+    out = torch.empty((Qp.shape[0], nprobe * G * s), dtype=torch.int64, device=index.codes.device)
+    for s0, cand in _shortlist_blocks(index, Qp, centers, G, s, nprobe, pack, block):
+        out[s0 : s0 + cand.shape[0]] = cand
+    return out
+
+
+def rerank(Q: torch.Tensor, X: torch.Tensor, cand: torch.Tensor, m: int) -> torch.Tensor:
+    """The ``m`` candidates of least exact squared distance to every query: int64 keys ``[nq, m]``,
+    ``d2 bits << 32 | row id``, ascending -- equal distances go to the lower row -- and
+    ``IVF_EMPTY_KEY`` behind them; :func:`mikmeans.ops.index_decode` decodes them.  ``Q`` ``[nq, F]`` and
+    ``X`` ``[n, F]`` (fewer than 2^32 rows) share a dtype (bfloat16 or float32) and a device; ``X`` may be
+    a slice with a longer row stride.  ``cand`` int64 ``[nq, R]``: an id outside ``[0, n)`` is an empty
+    slot, an id given twice gives its key twice.  ``d2`` is defined bit for bit (docs/PQ_INDEX.md):
+    sixteen accumulators over 16-byte pieces, subtract, multiply and add rounded one by one, NaN as one
+    pattern.  On the GPU csrc/rerank.hip writes one key per candidate and ``sort`` keeps the ``m``
+    smallest; CPU tensors run :func:`mikmeans.ops.cpu.rerank`."""
+    m = int(m)
+    if m < 1:
+        raise ValueError(f"rerank needs m >= 1, got m = {m}")
+    if Q.dim() != 2 or X.dim() != 2 or Q.shape[1] != X.shape[1] or Q.shape[1] < 1:
+        raise ValueError(f"rerank takes Q [nq, F] and X [n, F], got {tuple(Q.shape)} and {tuple(X.shape)}")
+    if Q.dtype != X.dtype or Q.dtype not in (torch.bfloat16, torch.float32) or Q.device != X.device:
+        raise ValueError(f"rerank takes bfloat16 or float32 queries and rows of one dtype on one device, got "
+                         f"{Q.dtype} on {Q.device} and {X.dtype} on {X.device}")
+    if X.shape[0] >= 1 << 32:
+        raise ValueError(f"rerank takes fewer than 2^32 rows, got {X.shape[0]}")
+    if cand.dim() != 2 or cand.shape[0] != Q.shape[0] or cand.shape[1] < 1 or cand.dtype != torch.int64:
+        raise ValueError(f"rerank takes candidates int64 [{Q.shape[0]}, R], R >= 1, got {cand.dtype} {tuple(cand.shape)}")
+    cand = cand.to(Q.device)
+    if not Q.is_cuda:
+        return cpu.rerank(Q, X, cand, m)
+    if Q.shape[1] > 1 and Q.stride(1) != 1:
+        Q = Q.contiguous()
+    if X.shape[1] > 1 and X.stride(1) != 1:
+        raise ValueError("rerank takes rows with unit column stride")
+    nq, R = cand.shape
+    keys = torch.empty((nq, R), dtype=torch.int64, device=Q.device)
+    require().rerank(Q, X, cand.contiguous(), keys)
+    keys = keys.sort(dim=1).values[:, :m]
+    if R >= m:
+        return keys
+    out = torch.full((nq, m), cpu.IVF_EMPTY_KEY, dtype=torch.int64, device=Q.device)
+    out[:, :R] = keys
+    return out
+
+
+def pq_refine(index: PQRowIndex, Q: torch.Tensor, centers: torch.Tensor, X: torch.Tensor, m: int, nprobe: int,
+              shortlist: int = INDEX_MAX_M, *, pack=None, block_queries: int | None = None) -> torch.Tensor:
+    """A PQ search re-ranked on the rows: the ``m`` rows of least exact distance among the
+    :func:`pq_shortlist` of every query, as :func:`rerank`'s keys ``[nq, m]``.  ``X`` ``[index.n, F]`` holds
+    the rows the index was built over, in the index's dtype: on the index's device it is read in
+    place; on the host (of a GPU index) every block of queries sends its candidate ids to the host
+    -- one host read a block -- where the distinct rows are gathered (``index_select``), cross to the
+    device once, and meet the same kernel through remapped ids: the same bits either way.  Queries
+    go through in blocks (:func:`pq_refine_block_queries`, or ``block_queries``); the result does not
+    depend on them."""
+    m, nprobe = int(m), int(nprobe)
+    if not 1 <= m <= INDEX_MAX_M:
+        raise ValueError(f"search needs 1 <= m <= {INDEX_MAX_M}, got m = {m}")
+    G, s = pq_shortlist_groups(shortlist)
+    Qp = _search_queries(index, Q, nprobe)
+    F, dev = index.F, index.codes.device
+    host = X.device != dev
+    if host and X.is_cuda:
+        raise ValueError(f"refine takes rows on {dev} or on the host, got {X.device}")
+    # (host rows of a GPU index may be of any dtype: the gathered rows are converted as they cross)
+    if X.dim() != 2 or tuple(X.shape) != (index.n, F) or (X.dtype != index.dtype and not host):
+        raise ValueError(f"refine takes the {index.n} indexed rows of {F} {index.dtype} features, got "
+                         f"{X.dtype} {tuple(X.shape)}")
+    block = (max(1, int(block_queries)) if block_queries
+             else pq_refine_block_queries(index.M, nprobe, F, G * s, host_rows=host, esize=X.element_size()))
+    keys = torch.empty((Qp.shape[0], m), dtype=torch.int64, device=dev)
+    for s0, cand in _shortlist_blocks(index, Qp, centers, G, s, nprobe, pack, block):
+        Qb = Qp[s0 : s0 + cand.shape[0], :F]
+        if not host:
+            keys[s0 : s0 + cand.shape[0]] = rerank(Qb, X, cand, m)
+            continue
+        ch = cand.cpu()                                                 # (the block's host read)
+        ids = torch.unique(ch[ch >= 0])                                 # ascending: local order = row order
+        staged = X.index_select(0, ids).to(device=dev, dtype=index.dtype)
+        local = torch.where(ch >= 0, torch.searchsorted(ids, ch.clamp(min=0)), -1).to(dev)
+        kb = rerank(Qb, staged, local, m)
+        back = ids.to(dev)[(kb & 0xFFFFFFFF).clamp(max=max(ids.numel() - 1, 0))] if ids.numel() else kb
+        keys[s0 : s0 + cand.shape[0]] = torch.where(kb == cpu.IVF_EMPTY_KEY, kb, (kb & ~0xFFFFFFFF) | back)
     return keys
 
 

@@ -616,6 +616,43 @@ def plan_pq_search(n: int, D: int, K: int, M: int, dtype="bfloat16", *, nq: int,
     return MemoryPlan("pq-index-search", n, D, Dp, K, "bfloat16" if es == 2 else "float32", p, tr)
 
 
+def pq_refine_block_queries(M: int, nprobe: int, F: int, shortlist: int, *, host_rows: bool = False,
+                            esize: int = 4) -> int:
+    """ops.pq_refine_block_queries: queries per block of a refined PQ search."""
+    R = int(nprobe) * int(shortlist)
+    per = int(nprobe) * (int(M) * PQ_KSUB * 4 + 8 * int(F) + 16 * int(shortlist)) + 32 * R
+    if host_rows:
+        per += R * (int(F) * int(esize) + 8)
+    return max(1, PQ_SCAN_BYTES // per)
+
+
+def plan_pq_refine(n: int, D: int, K: int, M: int, dtype="bfloat16", *, nq: int, m: int, nprobe: int,
+                   shortlist: int = 32, host_rows: bool = False) -> MemoryPlan:
+    """A refined PQ search (ops.pq_refine): :func:`plan_pq_search`'s terms with the scan at ``splits = G,
+    m = s`` (``G * s = shortlist`` keys a pair, decoded into as many candidate ids), per block of
+    queries (``pq_refine_block_queries``) the ``[B, R]`` re-rank keys, ``R = nprobe * shortlist``, with the
+    sort's copies and, for rows kept on the host, the staged rows (at most ``B * R``) and the remapped
+    ids.  Device rows are the caller's and are read in place."""
+    es = esize_of(dtype)
+    Dp = padded_cols(D, es)
+    dsp = padded_cols(D // M, es)
+    S = int(shortlist)
+    p = {**_pq_held(n, D, K, M), "result_keys": _r(nq * m * 8)}
+    B = min(int(nq), pq_refine_block_queries(M, nprobe, D, S, host_rows=host_rows, esize=es))
+    pairs = B * int(nprobe)
+    R = int(nprobe) * S
+    keys = _r(B * R * 8)
+    block = {"queries": _r(B * Dp * es), "query_norms": _r(B * 4), "probes": _r(2 * pairs * 4),
+             "probe_d2": _r(pairs * 4), "probe_centres": _r(pairs * D * 4), "residual_f32": _r(pairs * D * 4),
+             "residuals": _r(pairs * D * es), "slice": _r(pairs * dsp * es), "slice_norms": _r(pairs * 4),
+             "slice_d2": _r(pairs * PQ_KSUB * 4), "tables": _r(pairs * M * PQ_KSUB * 4), "shortlist_keys": keys,
+             "candidates": keys, "rerank_keys": keys, "sorted_keys": keys, "sort_order": keys,
+             "block_keys": _r(B * m * 8)}
+    if host_rows:
+        block.update({"staged_rows": _r(min(B * R, n) * D * es), "local_ids": keys, "staged_ids": _r(min(B * R, n) * 8)})
+    return MemoryPlan("pq-index-refine", n, D, Dp, K, "bfloat16" if es == 2 else "float32", p, {"block": block})
+
+
 # ------------------------------------------------------------------------ budget
 def hbm_budget(device=None) -> int:
     """Bytes a fit on ``device`` may allocate: ``MIKMEANS_HBM_BYTES`` when set, else the free

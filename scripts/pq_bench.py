@@ -16,9 +16,13 @@ after a warm pass.  It reports
                  first row is among the PQ search's m)
 * ``phases``  -- one block of the PQ search by phase: probes, residuals and tables, the scan kernel
                  (at every split count), the per-query sort
+* ``refine``  -- per ``--shortlist``: ``PQIndex.search(refine=)`` with device rows and with host rows (up to
+                 ``--host-candidates`` candidates), its recall@m against the flat search's rows, one block by
+                 phase (shortlist scan, re-rank kernel, sort) and the re-rank kernel beside the torch
+                 formulation ``((X[cand] - Q[:, None]) ** 2).sum(-1)``, alternating in one process
 
 Usage: ``python scripts/pq_bench.py [--out profiles/pq_bench.md] [--n 10000000] [--k 1024] [--pq 16]
-[--nq 1 1000 100000] [--nprobe 16] [--m 10] [--repeats 5] [--step-timeout 420]``
+[--nq 1 1000 100000] [--nprobe 16] [--m 10] [--shortlist 32 128 256] [--repeats 5] [--step-timeout 420]``
 """
 from __future__ import annotations
 
@@ -173,7 +177,70 @@ def step(a, nq: int, report_build: bool) -> int:
                       **{k: _stat(v) for k, v in ph.items()},
                       **{f"scan_splits_{s}": _stat(v) for s, v in scans.items()},
                       "block_code_bytes": int(sizes[probes[:nb]].sum()) * M}), flush=True)
+    _refined(a, nq, X, Q, C, pk, index, pqi, exact)
     return 0
+
+
+def _refined(a, nq, X, Q, C, pk, index, pqi, exact):
+    """``PQIndex.search(refine=)`` per shortlist, device rows and host rows: the whole search, its recall
+    against the flat search's rows, one block by phase (shortlist scan with its probes and tables, the
+    re-rank kernel, the sort) and the re-rank kernel beside the torch formulation
+    ``((X[cand] - Q[:, None]) ** 2).sum(-1)`` on the same candidates, the two alternating."""
+    import torch
+
+    from mikmeans import ops
+
+    m, M, nprobe, dev = a.m, a.pq, a.nprobe, X.device
+    C_ = ops.require()
+    Xh = None
+    for S in a.shortlist:
+        rec = {"what": "refine", "nq": nq, "shortlist": S, "candidates_per_query": nprobe * S}
+        pqi.search(Q, m, nprobe=nprobe, refine=X, shortlist=S)
+        td = []
+        for _ in range(a.repeats):
+            (rows, _), t = _timed(lambda: pqi.search(Q, m, nprobe=nprobe, refine=X, shortlist=S))
+            td.append(t)
+        rec["device_rows"] = _stat(td)
+        rec["device_queries_per_s"] = round(nq / (rec["device_rows"]["median_ms"] / 1e3), 1)
+        rec["recall_vs_flat"] = round(_recall(rows, exact), 4)
+        rec["flat_first_in_refined"] = round(float((rows == exact[:, :1]).any(1).float().mean()), 4)
+        # host rows: every block's distinct candidate rows are gathered on the host (long for many queries)
+        if nq * nprobe * S <= a.host_candidates:
+            if Xh is None:
+                Xh = X.cpu()
+            rh, _ = pqi.search(Q, m, nprobe=nprobe, refine=Xh, shortlist=S)
+            assert torch.equal(rh, rows)
+            th = []
+            for _ in range(a.repeats):
+                _, t = _timed(lambda: pqi.search(Q, m, nprobe=nprobe, refine=Xh, shortlist=S))
+                th.append(t)
+            rec["host_rows"] = _stat(th)
+        else:
+            rec["host_rows"] = "not measured"
+        # one block by phase
+        nb = min(nq, ops.pq_refine_block_queries(M, nprobe, D, S))
+        Qb = Q[:nb].contiguous()
+        ph = {"shortlist_scan": [], "rerank": [], "sort": [], "torch_formulation": []}
+        for r in range(a.repeats + 1):
+            cand, t0 = _timed(lambda: ops.pq_shortlist(index, Qb, C, S, nprobe, pack=pk, block_queries=nb))
+            keys = torch.empty(cand.shape, dtype=torch.int64, device=dev)
+            _, t1 = _timed(lambda: C_.rerank(Qb, X, cand, keys))
+            _, t2 = _timed(lambda: keys.sort(dim=1).values[:, :m])
+            # the torch formulation takes a [rows, R, D] temporary: in passes of at most 2^28 elements
+            step_q = max(1, (1 << 28) // (cand.shape[1] * D))
+
+            def formulation():
+                cc = cand.clamp(min=0)
+                return [((X[cc[s : s + step_q]] - Qb[s : s + step_q, None]) ** 2).sum(-1) for s in range(0, nb, step_q)]
+
+            _, t3 = _timed(formulation)
+            del cand, keys
+            if r:
+                for k, t in zip(ph, (t0, t1, t2, t3)):
+                    ph[k].append(t)
+        rec.update({"block_queries": nb, **{k: _stat(v) for k, v in ph.items()},
+                    "rerank_row_gb_per_s": round(nb * nprobe * S * D * 2 / (statistics.median(ph["rerank"]) / 1e3) / 1e9, 1)})
+        print(json.dumps(rec), flush=True)
 
 
 def main(argv=None) -> int:
@@ -187,6 +254,9 @@ def main(argv=None) -> int:
     ap.add_argument("--nq", type=int, nargs="+", default=[1, 1000, 100000])
     ap.add_argument("--nprobe", type=int, default=16)
     ap.add_argument("--m", type=int, default=10)
+    ap.add_argument("--shortlist", type=int, nargs="*", default=[32, 128, 256], help="refined searches to measure")
+    ap.add_argument("--host-candidates", type=int, default=1 << 24,
+                    help="host rows are measured up to this many candidates (nq * nprobe * shortlist)")
     ap.add_argument("--step-timeout", type=int, default=420, help="seconds one step (one query count) may take")
     ap.add_argument("--step", type=int, default=None, help=argparse.SUPPRESS)   # (a child: this query count)
     ap.add_argument("--report-build", action="store_true", help=argparse.SUPPRESS)
@@ -195,7 +265,8 @@ def main(argv=None) -> int:
         return step(a, a.step, a.report_build)
     recs = []
     base = [sys.executable, os.path.abspath(__file__), "--n", str(a.n), "--k", str(a.k), "--pq", str(a.pq), "--train-rows",
-            str(a.train_rows), "--nprobe", str(a.nprobe), "--m", str(a.m), "--repeats", str(a.repeats)]
+            str(a.train_rows), "--nprobe", str(a.nprobe), "--m", str(a.m), "--repeats", str(a.repeats),
+            "--host-candidates", str(a.host_candidates), "--shortlist", *map(str, a.shortlist)]
     for i, nq in enumerate(a.nq):
         cmd = ["timeout", "-k", "10", str(a.step_timeout), *base, "--step", str(nq), *(["--report-build"] if i == 0 else [])]
         r = subprocess.run(cmd, capture_output=True, text=True)
